@@ -9,6 +9,14 @@ shards like utils/split_scp.pl (make_FDLPspectrum_feats.sh:135-157): every rank 
 shard with no collective (scaling is weak).  Prints ONE JSON line on rank 0.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config wsj|reverb|chime4] [--workload wsj|librispeech|reverb]
+                    [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps of the headline (four batches in flight, inputs and outputs in
+HBM) and prints the result line: metric, value, unit, ms_per_step, dtype and the workload's config.
+--dump-outputs DIR then writes the float32 features of the last timed step (dump_outputs; the inputs and the
+jitter stream are seeded, so two builds run with the same arguments are comparable output for output).
+--full adds everything else to the line: the CPU baseline (cpu_baseline), the one-batch pass, the
+profiled pass behind the roofline, per-kernel and HBM figures, and the PCIe-inclusive pass (with_transfers).
 
 Configs (BASELINE.json configs[1..4]):
   wsj      WSJ params (M 100, range 0..100), 4 s speech-like utterances (workload wsj, the headline);
@@ -375,12 +383,12 @@ def xfer_child_spec(args, world, rank, local, argv=None, environ=None):
         if skip:
             skip = False
             continue
-        if a in ("--xfer-only", "--dry-run"):
+        if a in ("--xfer-only", "--dry-run", "--full"):
             continue
-        if a in ("--gpus", "--xfer-shard"):
+        if a in ("--gpus", "--xfer-shard", "--dump-outputs"):
             skip = True
             continue
-        if a.startswith("--gpus=") or a.startswith("--xfer-shard="):
+        if a.startswith("--gpus=") or a.startswith("--xfer-shard=") or a.startswith("--dump-outputs="):
             continue
         out.append(a)
     out += ["--xfer-only", "--no-cpu-baseline", "--gpus", "1", "--xfer-shard", "%d/%d" % (rank, world)]
@@ -593,6 +601,28 @@ def pcie_pass(args, plans, streams, pcms, outs, pcm_host, lens, nj, rng, mix, au
                     % (B, len(comp), S, nd)}
 
 
+DUMP_BYTES = 48 << 20  # --dump-outputs: float32 bytes written by all ranks together (64 MB at the most)
+DUMP_SEED = 20240
+
+
+def dump_outputs(path, outs, rank, world):
+    """--dump-outputs: the float32 feature rows [rows, bands] that every batch in flight holds after the last
+    timed step (what a caller of FdlpPlan.compute(..., out=) receives), one DIR/features_rank<r>_batch<b>.npy
+    per batch.  A batch with more rows than DUMP_BYTES allows is written as a sample of its rows: the same
+    seeded choice of row numbers, in ascending order, for every batch and every run of the same command."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    rows, D = outs[0].shape
+    n = max(1, DUMP_BYTES // (world * len(outs) * D * 4))
+    idx = None
+    if rows > n:
+        pick = np.sort(np.random.default_rng(DUMP_SEED).choice(rows, size=n, replace=False))
+        idx = torch.from_numpy(pick).to(outs[0].device)
+    for b, o in enumerate(outs):
+        a = (o if idx is None else o.index_select(0, idx)).cpu().numpy().astype(np.float32, copy=False)
+        np.save(os.path.join(path, "features_rank%d_batch%d.npy" % (rank, b)), a)
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -634,6 +664,14 @@ def parse_args(argv=None):
                          "(configs[4]); reverb: U(2,15) s reverberant sets (configs[2]); default from --config")
     ap.add_argument("--frames", type=int, default=4096, help="analysis frames per step per GPU (U(a,b) workloads)")
     ap.add_argument("--dry-run", action="store_true", help="launcher + sharding + reduction only, no device work")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline's timed steps also run the CPU baseline, the one-batch and profiled "
+                         "passes (roofline, per-kernel and HBM figures) and the PCIe-inclusive pass; a plain run "
+                         "times the headline only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write the features the last timed step computed to "
+                         "DIR/features_rank<r>_batch<b>.npy (float32 [rows, bands]; of a batch too large for "
+                         "DUMP_BYTES, a fixed seeded sample of the rows in ascending order)")
     a = ap.parse_args(argv)
     if a.workload is None:
         a.workload = {"wsj": "wsj", "reverb": "reverb", "chime4": "wsj"}[a.config]
@@ -674,19 +712,19 @@ def main():
     mine = shard_of(full, s_rank, s_world)
     first = sum(split_counts(len(full), s_world)[:s_rank])
 
-    # CPU baseline first (fork before any GPU initialisation in this process), rank 0 at N=1 only
+    # --full: CPU baseline first (fork before any GPU initialisation in this process), rank 0 at N=1 only
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.dry_run:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.dry_run:
         per = args.cpu_per_worker or (10 if args.config == "reverb" else 24)
         cpu = cpu_baseline(args.config, [t for _, t, _ in mine], args.cpu_workers, per, noise_host)
         cpu["workers_rule"] = ("--cpu-workers %d" % args.cpu_workers if args.cpu_workers != host_cores()
                                else "default: " + host_cores(with_rule=True)[1])
 
-    # PCIe-inclusive pass of every rank in a child process (before this process touches the GPU):
+    # --full: PCIe-inclusive pass of every rank in a child process (before this process touches the GPU):
     # GPU_MAX_HW_QUEUES is read once per process, and the headline keeps the process default.  The ranks'
     # children run at the same time, each on its own GPU, as the JOBs of a recipe run do.
     xfer_child = None
-    use_child = not args.no_transfers and not args.xfer_only and args.xfer_hw_queues > 0
+    use_child = args.full and not args.no_transfers and not args.xfer_only and args.xfer_hw_queues > 0
     if use_child and not args.dry_run:
         xfer_child = run_xfer_child(args, world, rank, local)
 
@@ -789,6 +827,48 @@ def main():
         elapsed = elapsed_one = elapsed_prof = None
     else:
         elapsed = timed_steps(step_inflight, args.steps, args.warmup, sync, dd, cpu_dev)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, outs, rank, world)
+        audio_h = world * args.steps * B * audio_s / 3600.0
+        value = audio_h / elapsed
+        ms_step = elapsed / args.steps * 1e3
+        path = plan.autocorr_path
+        res = {
+            "metric": METRIC,
+            "value": value,
+            "unit": "audio-hours/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": ms_step,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f64",
+            "data": "synthetic",
+            "config": {"workload": workload_name(args),
+                       "params": args.config,
+                       "scp_entries_total": len(full),
+                       "utts_per_step_per_gpu": B * len(lens),
+                       "batches_in_flight": B,
+                       "utts_per_batch": len(lens),
+                       "utt_seconds": args.seconds if args.workload == "wsj" else "%s, mean %.2f" % (
+                           "U(1,30)" if args.workload == "librispeech" else "U(2,15)", audio_s / max(len(lens), 1)),
+                       "frames_per_step_per_gpu": B * frames, "nfilters": cfg.nfilters, "order": cfg.order,
+                       "coeff_num": cfg.coeff_num, "coeff_range": cfg.coeff_range, "fbank": cfg.fbank_type,
+                       "support_eps": cfg.support_eps, "autocorr_path": path, "dct_path": plan.dct_path,
+                       "add_noise": "babble,%g (on the device, in the timed kernels)" % NOISE_SNR
+                       if noise_host is not None else "clean",
+                       "reverb_sets": ("1ch T60 0.7 s / 8ch_beamformit T60 0.35 s, synthetic RIRs applied by "
+                                       "fdlp_reverb before timing" if args.workload == "reverb" else None),
+                       "parallelism": "scp-shard x%d (contiguous split_scp shards, no collective)" % world},
+        }
+        if not args.full:  # a plain run: the headline only
+            if rank == 0:
+                print(json.dumps(res))
+            if world > 1:
+                dist.destroy_process_group()
+            return
 
     # 1b) one batch in flight (the same steps with B = 1), reported beside the headline
     if not args.xfer_only:
@@ -816,7 +896,7 @@ def main():
         dist.all_gather_object(got, xfer_child)
         xfer_child = combine_xfer_children(got)
     xfer = xfer_child
-    if not args.no_transfers and xfer_child is None:
+    if (args.full or args.xfer_only) and not args.no_transfers and xfer_child is None:
         xfer = pcie_pass(args, plans, streams, pcms, outs, pcm_host, lens, nj, rng, mix, audio_s, world, dd,
                          sync, dev, B)
 
@@ -824,9 +904,6 @@ def main():
         xfer["hw_queues"] = os.environ.get("GPU_MAX_HW_QUEUES", "default")
         print(json.dumps({"with_transfers": xfer}))
         return
-    audio_h = world * args.steps * B * audio_s / 3600.0
-    value = audio_h / elapsed
-    ms_step = elapsed / args.steps * 1e3
     # dominant stage of the one-batch profiled pass (fdlp_stage_times: HIP events on the kernels' stream);
     # its algorithmic FLOPs are the useful work of the algorithm that stage runs (DESIGN.md "Measurement")
     sms = {k: v / max(ncalls, 1) for k, v in stages.items()}
@@ -847,7 +924,6 @@ def main():
                    "lpc_env": lpc_flops(cfg.order, cfg.coeff_num, Me, plan.kk) * items,
                    "ola_log": 2.0 * items * plan.kk}
     pmc_file = _latest_pmc(args.config if args.workload != "librispeech" else "librispeech") or PMC_FILE
-    path = plan.autocorr_path
     traffic, bound = stage_pmc(stage_kernel_prefixes(dom, path), pmc_file)
     dom_ms = sum(dom_kernels.values()) if dom_kernels else stage_ms[dom]
     achieved = stage_flops[dom] / (dom_ms * 1e-3) / 1e12
@@ -867,35 +943,7 @@ def main():
                              "passes of this command, %s" % os.path.relpath(pmc_file or "none", ROOT),
            "note": "the path is fp64-compute-bound; HBM does not bound it (SURVEY.md 8(d))"}
     desc = STAGE_DESC[dom]
-    res = {
-        "metric": METRIC,
-        "value": value,
-        "unit": "audio-hours/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": ms_step,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic",
-        "config": {"workload": workload_name(args),
-                   "params": args.config,
-                   "scp_entries_total": len(full),
-                   "utts_per_step_per_gpu": B * len(lens),
-                   "batches_in_flight": B,
-                   "utts_per_batch": len(lens),
-                   "utt_seconds": args.seconds if args.workload == "wsj" else "%s, mean %.2f" % (
-                       "U(1,30)" if args.workload == "librispeech" else "U(2,15)", audio_s / max(len(lens), 1)),
-                   "frames_per_step_per_gpu": B * frames, "nfilters": cfg.nfilters, "order": cfg.order,
-                   "coeff_num": cfg.coeff_num, "coeff_range": cfg.coeff_range, "fbank": cfg.fbank_type,
-                   "support_eps": cfg.support_eps, "autocorr_path": path, "dct_path": plan.dct_path,
-                   "add_noise": "babble,%g (on the device, in the timed kernels)" % NOISE_SNR
-                   if noise_host is not None else "clean",
-                   "reverb_sets": ("1ch T60 0.7 s / 8ch_beamformit T60 0.35 s, synthetic RIRs applied by "
-                                   "fdlp_reverb before timing" if args.workload == "reverb" else None),
-                   "parallelism": "scp-shard x%d (contiguous split_scp shards, no collective)" % world},
+    res.update({
         "roofline": {"bound": bound or "fp64-valu", "stage": dom,
                      "kernel": desc[path] if isinstance(desc, dict) else desc,
                      "achieved": achieved, "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s",
@@ -935,7 +983,7 @@ def main():
         "sect8d_first_h2d_to_last_d2h": ({"value": xfer["value"], "unit": "audio-hours/s",
                                           "ratio_to_value": xfer["value"] / value} if xfer else None),
         "cpu_baseline": cpu,
-    }
+    })
     if rank == 0:
         print(json.dumps(res))
     if world > 1:

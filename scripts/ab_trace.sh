@@ -19,7 +19,7 @@ for round in $(seq 1 ${ROUNDS:-1}); do
       done
     fi
     d=gpurun_out/ab/r${round}v$i
-    env "${envs[@]}" timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $d -o run -- python3 bench.py $BARGS "${args[@]}" \
+    env "${envs[@]}" timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $d -o run -- python3 bench.py --full $BARGS "${args[@]}" \
       > $d.log 2>&1 || { echo "variant $v failed"; tail -20 $d.log; exit 3; }
     echo "== [$round] $v  $(grep -o '"value": [0-9.]*' $d.log | head -1)"
     python3 - "$(find $d -name '*.db' | head -1)" <<'PY'

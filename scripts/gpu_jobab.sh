@@ -11,7 +11,7 @@ for round in 1 2; do
   for lib in "$LIB_A" "$LIB_B"; do
     n=$(basename $lib .so)
     FDLP_LIB=$lib timeout -k 10 200 python3 -u benchmarks/driver_e2e.py --utts 1800 --nj 8 --jobs-per-gpu 4 --trace-dir $O/tr_${n}_$round > $O/e2e_${n}_$round.json 2> $O/e2e.err || { tail -20 $O/e2e.err; exit 2; }
-    FDLP_LIB=$lib timeout -k 10 300 python3 bench.py --no-cpu-baseline ${BENCH_EXTRA:-} > $O/bench_run.log 2>&1 || { tail -20 $O/bench_run.log; exit 3; }
+    FDLP_LIB=$lib timeout -k 10 300 python3 bench.py --full --no-cpu-baseline ${BENCH_EXTRA:-} > $O/bench_run.log 2>&1 || { tail -20 $O/bench_run.log; exit 3; }
     python3 -c "
 import json,sys
 e=json.loads(open(sys.argv[2]).read().strip().splitlines()[-1]); d=json.loads(open(sys.argv[3]).read().strip().splitlines()[-1])

@@ -32,7 +32,7 @@ for k,m in d.items():
 " gpurun_out/evidence_$TAG/pmc.json
 fi
 if [ -z "${NO_WSJ_BENCH:-}" ]; then
-  timeout -k 10 600 python3 bench.py > $O/bench_full.log 2>&1 || { echo "bench failed"; tail -20 $O/bench_full.log; exit 5; }
+  timeout -k 10 600 python3 bench.py --full > $O/bench_full.log 2>&1 || { echo "bench failed"; tail -20 $O/bench_full.log; exit 5; }
   tail -1 $O/bench_full.log > $O/bench_full.json
 fi
 if [ -n "${REVERB_PMC:-}" ]; then  # the REVERB trace + PMC passes -> profiles/${TAG}_reverb_pmc.json (the REVERB line's traffic)
@@ -40,11 +40,11 @@ if [ -n "${REVERB_PMC:-}" ]; then  # the REVERB trace + PMC passes -> profiles/$
     BENCH_ARGS="--config reverb --steps 3 --warmup 1 --no-cpu-baseline --inflight 1 --no-transfers" bash scripts/round_evidence.sh || exit 7
 fi
 if [ -n "${LIBRI:-}" ]; then
-  timeout -k 10 400 python3 bench.py --workload librispeech --no-cpu-baseline > $O/bench_librispeech.log 2>&1 || { echo "bench librispeech failed"; tail -30 $O/bench_librispeech.log; exit 8; }
+  timeout -k 10 400 python3 bench.py --full --workload librispeech --no-cpu-baseline > $O/bench_librispeech.log 2>&1 || { echo "bench librispeech failed"; tail -30 $O/bench_librispeech.log; exit 8; }
   tail -1 $O/bench_librispeech.log > $O/bench_librispeech.json
 fi
 for c in ${CONFIGS-reverb chime4}; do
-  timeout -k 10 400 python3 bench.py --config $c --no-cpu-baseline > $O/bench_$c.log 2>&1 || { echo "bench $c failed"; tail -30 $O/bench_$c.log; exit 6; }
+  timeout -k 10 400 python3 bench.py --full --config $c --no-cpu-baseline > $O/bench_$c.log 2>&1 || { echo "bench $c failed"; tail -30 $O/bench_$c.log; exit 6; }
   tail -1 $O/bench_$c.log > $O/bench_$c.json
 done
 for f in $O/bench_*.json; do

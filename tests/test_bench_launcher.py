@@ -47,18 +47,50 @@ def test_dry_run_librispeech_shards_balance_frames():
 def test_every_rank_gets_its_pcie_child(gpus):
     """The PCIe-inclusive pass (with_transfers, SURVEY 8(d) "first H2D to last D2H") runs in a child process
     of every rank, started before the rank touches the GPU: single-process argv over the rank's own shard,
-    GPU_MAX_HW_QUEUES raised, the rank's GPU only, no rendezvous variables."""
-    res = _run("--gpus", str(gpus), "--utts", "5")
+    GPU_MAX_HW_QUEUES raised, the rank's GPU only, no rendezvous variables.  The pass belongs to --full."""
+    res = _run("--gpus", str(gpus), "--utts", "5", "--full", "--dump-outputs", "unused")
     ch = res["xfer_children"]
     assert len(ch) == gpus
     for r, c in enumerate(ch):
         a = c["argv"]
         assert "--xfer-only" in a and "--dry-run" not in a
+        assert "--full" not in a and "--dump-outputs" not in a and "unused" not in a
         assert a[a.index("--gpus") + 1] == "1" and a.count("--gpus") == 1
         assert a[a.index("--xfer-shard") + 1] == "%d/%d" % (r, gpus)
         assert c["env"]["GPU_MAX_HW_QUEUES"] == "8"
         assert c["env"]["HIP_VISIBLE_DEVICES"] == (str(r) if gpus > 1 else os.environ.get("HIP_VISIBLE_DEVICES"))
         assert c["rank_env_dropped"] and c["before_gpu_init"]
+
+
+def test_plain_run_starts_no_pcie_child():
+    """Without --full the benchmark times the headline only: no rank gets a PCIe-pass child."""
+    assert _run("--gpus", "2", "--utts", "5")["xfer_children"] == [None, None]
+
+
+def test_dump_outputs_writes_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: float32 [rows, bands] per batch; a batch too large for DUMP_BYTES is written as the same
+    seeded, ascending choice of rows for every batch and every call."""
+    import numpy as np
+    import torch
+    b = _bench_module()
+    g = torch.Generator().manual_seed(1)
+    outs = [torch.randn(300, 80, generator=g), torch.randn(300, 80, generator=g)]
+    b.dump_outputs(str(tmp_path / "all"), outs, 0, 1)
+    for k, o in enumerate(outs):
+        a = np.load(tmp_path / "all" / ("features_rank0_batch%d.npy" % k))
+        assert a.dtype == np.float32 and np.array_equal(a, o.numpy())
+    assert b.DUMP_BYTES <= 64 << 20
+    monkeypatch.setattr(b, "DUMP_BYTES", 2 * 100 * 80 * 4)  # 100 of the 300 rows of each batch
+    b.dump_outputs(str(tmp_path / "s1"), outs, 3, 1)
+    b.dump_outputs(str(tmp_path / "s2"), outs, 3, 1)
+    pick = np.sort(np.random.default_rng(b.DUMP_SEED).choice(300, size=100, replace=False))
+    tot = 0
+    for k, o in enumerate(outs):
+        a = np.load(tmp_path / "s1" / ("features_rank3_batch%d.npy" % k))
+        assert a.dtype == np.float32 and np.array_equal(a, o.numpy()[pick])
+        assert np.array_equal(a, np.load(tmp_path / "s2" / ("features_rank3_batch%d.npy" % k)))
+        tot += a.nbytes
+    assert tot <= b.DUMP_BYTES
 
 
 def test_pcie_children_combine():
