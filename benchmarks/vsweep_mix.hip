@@ -3,6 +3,9 @@
 //   fma   : broadcasts from registers (no DPP), window in registers
 //   dpp   : 10 row_newbcast broadcasts per block (bound_ctrl), window in registers
 //   lds   : dpp + the window's A new values and cur read from an LDS ring each block (two banks)
+//   ldsdpp / ldsrev / ldsrev0 / ldsrevc : the kernel's own block (v_fmac_f64_dpp broadcasts,
+//           window reads at the block head) in two FMA orders, see krev below
+// The ring rows are 544 doubles, the kernel's conflict-free stride.
 // Build: hipcc -O3 --offload-arch=gfx950 benchmarks/vsweep_mix.hip -o benchmarks/vsweep_mix
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -23,9 +26,9 @@ __device__ __forceinline__ void block(double (&acc)[A], const double (&bb)[A], c
 
 template <int MODE>
 __global__ __launch_bounds__(64, 2) void k(const double* in, double* out, int iters) {
-  __shared__ double ring[4][528];
+  __shared__ double ring[4][544];
   const int l = threadIdx.x & 15, row = threadIdx.x >> 4;
-  for (int q = l; q < 528; q += 16) ring[row][q] = in[(q + row) & 255] + 1e-3 * q;
+  for (int q = l; q < 544; q += 16) ring[row][q] = in[(q + row) & 255] + 1e-3 * q;
   __syncthreads();
   double acc[A], X[A], Y[A], bb[A];
   for (int u = 0; u < A; ++u) { acc[u] = 0; X[u] = in[u + l]; Y[u] = in[u + 20 + l]; bb[u] = in[u + 40]; }
@@ -57,9 +60,9 @@ __global__ __launch_bounds__(64, 2) void k(const double* in, double* out, int it
 // ldspf: as lds, but each block's window (and broadcast source) is read one block ahead into a third
 // register bank, so the wait at a block head is for reads issued a whole block earlier
 __global__ __launch_bounds__(64, 2) void kpf(const double* in, double* out, int iters) {
-  __shared__ double ring[4][528];
+  __shared__ double ring[4][544];
   const int l = threadIdx.x & 15, row = threadIdx.x >> 4;
-  for (int q = l; q < 528; q += 16) ring[row][q] = in[(q + row) & 255] + 1e-3 * q;
+  for (int q = l; q < 544; q += 16) ring[row][q] = in[(q + row) & 255] + 1e-3 * q;
   __syncthreads();
   double acc[A], B0[A], B1[A], B2[A], bb[A];
   for (int u = 0; u < A; ++u) { acc[u] = 0; B0[u] = in[u + l]; B2[u] = in[u + 20 + l]; bb[u] = in[u + 40]; }
@@ -98,9 +101,9 @@ __device__ __forceinline__ void shift_in(double (&dst)[A], const double (&src)[A
   for (int q = 0; q < A; ++q) dst[q] = __builtin_amdgcn_update_dpp(nv[q], src[q], 0x111, 0xF, 0xF, false);
 }
 __global__ __launch_bounds__(64, 2) void kdw(const double* in, double* out, int iters) {
-  __shared__ double ring[4][528];
+  __shared__ double ring[4][544];
   const int l = threadIdx.x & 15, row = threadIdx.x >> 4;
-  for (int q = l; q < 528; q += 16) ring[row][q] = in[(q + row) & 255] + 1e-3 * q;
+  for (int q = l; q < 544; q += 16) ring[row][q] = in[(q + row) & 255] + 1e-3 * q;
   __syncthreads();
   double acc[A], X[A], Y[A], bb[A], nv[A];
   for (int u = 0; u < A; ++u) { acc[u] = 0; X[u] = in[u + l]; Y[u] = in[u + 20 + l]; bb[u] = in[u + 40]; nv[u] = 0; }
@@ -129,9 +132,87 @@ __global__ __launch_bounds__(64, 2) void kdw(const double* in, double* out, int 
   out[blockIdx.x * 64 + threadIdx.x] = s;
 }
 
+// krev: the block as ac_vsweep_kernel issues it (one v_fmac_f64_dpp per product, the ten window reads at
+// the block head; the compiler emits them in address order, lo[0:1] first) with the FMAs in one of two orders:
+//   ORDER 0  rows v = 0..A-1, u fastest: the first FMA reads lo[0], a value that was just read
+//   ORDER 1  the 45 products of the previous block's bank first (by window element, so consecutive FMAs
+//            write distinct accumulators), then the new bank by window element from lo[0] up, the order in
+//            which the reads return: the partial lgkmcnt waits release them pair by pair
+// STRICT: the FMAs are volatile and keep that order (ldsrev, ldsrev0).  Without it (ldsrevc) the scheduler
+// spreads the new-bank products among the old-bank ones: 9 FMAs, the wait for lo[0:1], 18 FMAs, the wait
+// for lo[2:3], and so on.
+// AHEAD: cur (the DPP source) comes from a read issued one block earlier (2 more VGPRs); otherwise it is
+// read in the block itself.
+template <int V, bool STRICT>
+__device__ __forceinline__ void fmac_bcast(double& acc, double cur, double w) {
+  if constexpr (STRICT)
+    asm volatile("v_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(cur), "v"(w), "n"(V));
+  else
+    asm("v_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(cur), "v"(w), "n"(V));
+}
+struct Order { int v[A * A], u[A * A]; };
+template <int ORDER>
+constexpr Order make_order() {
+  Order o{};
+  int n = 0;
+  if (ORDER == 0) {
+    for (int v = 0; v < A; ++v)
+      for (int u = 0; u < A; ++u) { o.v[n] = v; o.u[n] = u; ++n; }
+    return o;
+  }
+  // old group w: the products with hi[w], u = A-1 .. w+1; new group q: the products with lo[q], u = q .. 0
+  for (int w = 0; w < A - 1; ++w)
+    for (int u = A - 1; u > w; --u) { o.v[n] = A + w - u; o.u[n] = u; ++n; }
+  for (int q = 0; q < A; ++q)
+    for (int u = q; u >= 0; --u) { o.v[n] = q - u; o.u[n] = u; ++n; }
+  return o;
+}
+template <int ORDER, bool STRICT, int I = 0>
+__device__ __forceinline__ void fma_seq(double (&acc)[A], double cm, const double (&lo)[A], const double (&hi)[A]) {
+  if constexpr (I < A * A) {
+    constexpr Order o = make_order<ORDER>();
+    constexpr int v = o.v[I], u = o.u[I];
+    fmac_bcast<v, STRICT>(acc[u], cm, (v + u < A) ? lo[v + u] : hi[v + u - A]);
+    fma_seq<ORDER, STRICT, I + 1>(acc, cm, lo, hi);
+  }
+}
+template <int ORDER, bool AHEAD, bool STRICT>
+__global__ __launch_bounds__(64, 2) void krev(const double* in, double* out, int iters) {
+  __shared__ double ring[4][544];
+  const int l = threadIdx.x & 15, row = threadIdx.x >> 4;
+  for (int q = l; q < 544; q += 16) ring[row][q] = in[(q + row) & 255] + 1e-3 * q;
+  __syncthreads();
+  double acc[A], X[A], Y[A];
+  for (int u = 0; u < A; ++u) { acc[u] = 0; X[u] = in[u + l]; Y[u] = in[u + 20 + l]; }
+  double cur = ring[row][l];
+  auto blk = [&](int n0, double (&lo)[A], const double (&hi)[A]) {
+    double c;
+    if constexpr (!AHEAD) c = ring[row][(n0 + l) & 511];
+    const int base = (n0 + A * l) & 510;
+#pragma unroll
+    for (int q = 0; q < A; ++q) lo[q] = ring[row][base + q];
+    if constexpr (AHEAD) { c = cur; cur = ring[row][(n0 + A + l) & 511]; }
+    double cm;
+    asm volatile("v_mov_b64 %0, %1\n\ts_nop 1" : "=v"(cm) : "v"(c));
+    fma_seq<ORDER, STRICT>(acc, cm, lo, hi);
+  };
+  for (int it = 0; it < iters; ++it) {
+    const int n0 = (it * 2 * A) & 511;
+    blk(n0, X, Y);
+    blk(n0 + A, Y, X);
+  }
+  double s = 0;
+  for (int u = 0; u < A; ++u) s += acc[u];
+  out[blockIdx.x * 64 + threadIdx.x] = s;
+}
+
 template <int MODE>
 static void launch(dim3 g, const double* in, double* out, int iters) {
-  if constexpr (MODE == 4) hipLaunchKernelGGL(kdw, g, dim3(64), 0, 0, in, out, iters);
+  if constexpr (MODE == 5) hipLaunchKernelGGL((krev<0, false, false>), g, dim3(64), 0, 0, in, out, iters);
+  else if constexpr (MODE == 6) hipLaunchKernelGGL((krev<1, true, true>), g, dim3(64), 0, 0, in, out, iters);
+  else if constexpr (MODE == 7) hipLaunchKernelGGL((krev<1, false, true>), g, dim3(64), 0, 0, in, out, iters);
+  else if constexpr (MODE == 8) hipLaunchKernelGGL((krev<1, true, false>), g, dim3(64), 0, 0, in, out, iters);
+  else if constexpr (MODE == 4) hipLaunchKernelGGL(kdw, g, dim3(64), 0, 0, in, out, iters);
   else if constexpr (MODE == 3) hipLaunchKernelGGL(kpf, g, dim3(64), 0, 0, in, out, iters);
   else hipLaunchKernelGGL(k<MODE>, g, dim3(64), 0, 0, in, out, iters);
 }
@@ -147,7 +228,7 @@ static void run(const char* name, const double* in, double* out, int waves, int 
   float ms = 0;
   hipEventElapsedTime(&ms, a, b);
   const double flops = (MODE == 3 ? 1.0 : 2.0) * 2 * A * A * 64.0 * waves * (double)iters;  // kpf: one block per it
-  printf("%-6s waves %5d  %.3f ms  %.1f TFLOP/s\n", name, waves, ms, flops / ms / 1e9);
+  printf("%-8s waves %5d  %.3f ms  %.1f TFLOP/s\n", name, waves, ms, flops / ms / 1e9);
 }
 
 int main() {
@@ -163,6 +244,10 @@ int main() {
     run<2>("lds", in, out, waves, 20000);
     run<3>("ldspf", in, out, waves, 40002);
     run<4>("dppwin", in, out, waves, 20000);
+    run<5>("ldsdpp", in, out, waves, 20000);
+    run<6>("ldsrev", in, out, waves, 20000);
+    run<7>("ldsrev0", in, out, waves, 20000);
+    run<8>("ldsrevc", in, out, waves, 20000);
   }
   return 0;
 }

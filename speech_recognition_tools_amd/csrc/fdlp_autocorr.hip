@@ -693,12 +693,47 @@ constexpr int vs_chunk() { return (C == 0 && 18 * A < vs_ring<C>() - 256) ? 256 
 template <int C>
 constexpr int vs_waves_per_simd() { return 2; }
 
-template <int A, int V = 0>
+// The order in which a block issues its A x A products (v = position in the block, the DPP broadcast lane;
+// u = accumulator; window element v + u).  The A (A-1) / 2 products whose window element lies in the
+// previous block's bank (v + u >= A) need nothing that the block has just read from the ring, so they come
+// first and run while the window reads return; then the new bank from lo[0] up, the order in which the
+// reads are issued (address order; in the kernel one wait after the old bank takes them all in, see the
+// block's head).  Within either
+// half the products are grouped by window element: the FMAs of a group write distinct accumulators, and two
+// FMAs of one accumulator are at least two instructions apart.  (Rows v = 0 .. A-1 with u fastest, the
+// earlier order, put lo[0] into the block's first FMA, right behind the wait for all of its reads.)  The FMAs
+// are issued with fmac_bcast_ordered: left to itself the scheduler spreads the new-bank products among the
+// old-bank ones, nine FMAs ahead of the first wait.
+template <int A>
+struct VsOrder {
+  int v[A * A], u[A * A];
+};
+template <int A>
+constexpr VsOrder<A> vs_order() {
+  VsOrder<A> o{};
+  int n = 0;
+  for (int w = 0; w < A - 1; ++w)  // hi[w]: u = A-1 .. w+1
+    for (int u = A - 1; u > w; --u) {
+      o.v[n] = A + w - u;
+      o.u[n] = u;
+      ++n;
+    }
+  for (int q = 0; q < A; ++q)  // lo[q]: u = q .. 0
+    for (int u = q; u >= 0; --u) {
+      o.v[n] = q - u;
+      o.u[n] = u;
+      ++n;
+    }
+  return o;
+}
+template <int A, int I = 0>
 __device__ __forceinline__ void vs_fma_rows(double (&acc)[A], double cur, const double (&lo)[A], const double (&hi)[A]) {
-  if constexpr (V < A) {
-#pragma unroll
-    for (int u = 0; u < A; ++u) fmac_bcast<V>(acc[u], cur, (V + u < A) ? lo[V + u] : hi[V + u - A]);
-    vs_fma_rows<A, V + 1>(acc, cur, lo, hi);
+  if constexpr (I < A * A) {
+    constexpr VsOrder<A> o = vs_order<A>();
+    constexpr int V = o.v[I], U = o.u[I];
+    static_assert(V >= 0 && V < A && U >= 0 && U < A, "block order");
+    fmac_bcast_ordered<V>(acc[U], cur, (V + U < A) ? lo[V + U] : hi[V + U - A]);
+    vs_fma_rows<A, I + 1>(acc, cur, lo, hi);
   }
 }
 template <int A>
@@ -934,14 +969,38 @@ __global__ __launch_bounds__(64, vs_waves_per_simd<C>()) void ac_vsweep_kernel(D
   int k = kbeg;
   // event records are read with scalar loads: the index is wave-uniform, readfirstlane says so (a
   // vector load here would wait for the outstanding prefetch at every event)
-  auto ev_S = [&](int kk) -> int {
+  // Two whole records are held in scalar registers: event k (ev*, the next to fire) and event k + 1 (nx*).
+  // When event k has been handled, nx* becomes ev* and the record of k + 2 is requested; it is first
+  // looked at when event k + 1 has fired, so neither the loop conditions (evS) nor the handling of an
+  // event wait for memory.  evS = -1 past the last event.  The request is unconditional, of a clamped
+  // index (there is at least one record: B >= 1), and whether it was of a real event is kept apart
+  // (nxOk): a branch round the load, or a select on its result, would wait for it where it is issued.
+  // The requested record stays the four words of its load until it becomes ev* (a record carried round
+  // the loop field by field is copied out of the load's registers, and waited for, where it is issued);
+  // K is put together from its two words when it is used.
+  typedef int VsRec __attribute__((ext_vector_type(4), aligned(4)));
+  static_assert(sizeof(SkSnap) == 16 && sizeof(FlatEv) == 16, "event records are four words");
+  int evS = -1, evBand = 0, evW2 = 0, evW3 = 0;  // words 2, 3: K (skirts); type, chain (flat)
+  VsRec nx = {-1, 0, 0, 0};
+  bool nxOk = false;
+  auto ev_load = [&](int kk) __attribute__((always_inline)) {
     kk = __builtin_amdgcn_readfirstlane(kk);
-    if (kk >= kend) return -1;
-    return kind == 2 ? fev[kk].S : snaps[__builtin_amdgcn_readfirstlane(kind * B + kk)].S;
+    nxOk = kk < kend;
+    const int ki = max(min(kk, kend - 1), 0);
+    if constexpr (C > 0) nx = *reinterpret_cast<const VsRec*>(fev + ki);
+    else nx = *reinterpret_cast<const VsRec*>(snaps + __builtin_amdgcn_readfirstlane(kind * B + ki));
   };
-  int evS = ev_S(k);
+  auto ev_next = [&]() __attribute__((always_inline)) {
+    evS = nxOk ? nx.x : -1;
+    evBand = nx.y, evW2 = nx.z, evW3 = nx.w;
+    ev_load(k + 1);
+  };
+  ev_load(k);
+  ev_next();
   // all events at position S (positions >= S consumed)
-  auto handle_at = [&](int S) {
+  // (always_inline: out of line, as the inliner leaves it with six or more chains, the accumulators, chains and
+  // parked rows it captures live in scratch memory)
+  auto handle_at = [&](int S) __attribute__((always_inline)) {
     if constexpr (C > 0) {  // flat: fold the positions since the last event into every chain
 #pragma unroll
       for (int cc = 0; cc < C; ++cc)
@@ -952,33 +1011,45 @@ __global__ __launch_bounds__(64, vs_waves_per_simd<C>()) void ac_vsweep_kernel(D
     }
     while (evS == S) {
       if constexpr (C > 0) {
-        const FlatEv e = fev[__builtin_amdgcn_readfirstlane(k)];
 #pragma unroll
         for (int cc = 0; cc < C; ++cc) {
-          if (cc == e.chain) {
-            if (e.type == 1) push(ch[cc], 1.0, e.band);
+          if (cc == evW3) {
+            if (evW2 == 1) push(ch[cc], 1.0, evBand);
 #pragma unroll
-            for (int u = 0; u < A; ++u) ch[cc][u] = e.type == 0 ? 0.0 : ch[cc][u];
+            for (int u = 0; u < A; ++u) ch[cc][u] = evW2 == 0 ? 0.0 : ch[cc][u];
           }
         }
       } else {
-        const SkSnap e = snaps[__builtin_amdgcn_readfirstlane(kind * B + k)];
-        push(acc, e.K, e.band);
+        push(acc, __hiloint2double(__builtin_amdgcn_readfirstlane(evW3), __builtin_amdgcn_readfirstlane(evW2)), evBand);
       }
       ++k;
-      evS = ev_S(k);
+      ev_next();
     }
   };
 
   // one block [n0, n0 + A): positions at or above a pending event are consumed first (masked pass),
   // then the event is handled; usually a single unmasked pass
+  // The window and cur (the DPP source, also the masked select) are read once per block, before the pass
+  // loop.  cur comes from a read issued one block earlier (cur_ahead, 2 VGPRs), so the block's first FMAs,
+  // which need only cur and the previous bank, wait for no read of this block.  The ring is therefore
+  // staged one block ahead, which it has room for.
+  static_assert(19 * A < kVsRing - kVsChunk, "ring room for staging one block ahead");
+  double cur_ahead = rg[slot_add(A * b_top, l)];
   auto block = [&](int n0, double (&lo)[A], const double (&hi)[A]) {
-    ensure(n0);
+    const int n1 = max(n0 - A, A * b_bot);  // the next block (this one again at the sweep's end)
+    ensure(n1);
+    // The record requested at the last event (at the latest in the previous block) is taken in here, while
+    // no ring read is outstanding: scalar loads return out of order, and a wait that may have one pending
+    // cannot count the ring reads, it waits for them all.
+    asm volatile("" ::"s"(nx));
+    // likewise cur's read, a block old: taken in before this block's reads are issued
+    asm volatile("" : "+v"(cur_ahead));
     const int base = slot_add(n0, A * l);
     FDLP_CHECK(base >= 0 && base + A <= kVsRing + kVsMirror);
 #pragma unroll
     for (int q = 0; q < A; ++q) lo[q] = rg[base + q];
-    const double cur = rg[slot_add(n0, l)];
+    const double cur = cur_ahead;
+    cur_ahead = rg[slot_add(n1, l)];
     const int pos = n0 + l;
     int hi_m = min(n0 + A, nhi);
     for (;;) {

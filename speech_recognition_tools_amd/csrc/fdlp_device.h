@@ -210,6 +210,14 @@ template <int V>
 __device__ __forceinline__ void fmac_bcast(double& acc, double cur, double w) {
   asm("v_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(cur), "v"(w), "n"(V));
 }
+// The same, kept in program order among its kind (volatile): for sequences whose order is chosen against
+// the latency of their operands' loads, which the scheduler would otherwise rearrange.
+template <int V>
+__device__ __forceinline__ void fmac_bcast_ordered(double& acc, double cur, double w) {
+  asm volatile("v_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf"
+               : "+v"(acc)
+               : "v"(cur), "v"(w), "n"(V));
+}
 
 // LDS read of one double at a compile-time byte offset from a per-lane byte address.  Plain
 // ds_read_b64 (2 LDS cycles per wave when conflict-free); the compiler would otherwise merge the
