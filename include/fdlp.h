@@ -281,6 +281,38 @@ int fdlp_mel_geometry(const fdlp_mel_plan* plan, int64_t T, int32_t* F);
  * out_row, optional fp64 copy, ark_decimals; `jitter` is unused). */
 int fdlp_mel_compute(fdlp_mel_plan* plan, const fdlp_batch* batch, void* stream);
 
+/* ---- sibling feature: MFCC (src/featgen/computeMfccFeatures.py, make_mfcc_feats.sh) ------- */
+/* Replaces extractMelEnergyFeats (computeMfccFeatures.py:58-135): signal / 2^15, getFrames with np.hamming(L),
+ * |scipy.fftpack.fft(frame, n)| with n = nfft/2 + 1 (a DFT of arbitrary length: 513 at the defaults; a longer
+ * frame is truncated to n samples), all n bins @ createFbank(nfilters, nfft, srate).T, log10,
+ * scipy.fftpack.dct (type 2, unnormalised)[:, :13], then spliceFeats(context) whose last `context` rows of
+ * an utterance stay zero.  The DFT is a dense GEMM on the fp64 MFMA; the work tile lives in the 160 KB LDS,
+ * which bounds the sizes: max(min(L, n), nfilters) + n/2 <= ~1230 (L = srate * fduration), e.g. nfft <= 2048
+ * with 20 ms frames; larger configurations are FDLP_E_INVALID. */
+typedef struct fdlp_mfcc_config {
+  int32_t nfilters;          /* --nfilters (30); >= 1                                   (:142)  */
+  int32_t nfft;              /* --nfft (1024); even, no smoothness condition            (:146)  */
+  int32_t frate;             /* --frate (100)                                           (:144)  */
+  int32_t srate;             /* 16000                                                   (:58)   */
+  double fduration;          /* --fduration (0.02)                                      (:143)  */
+  int32_t context;           /* --context (0 = no splicing)                             (:145)  */
+  int32_t max_frames;        /* frames per fdlp_mfcc_compute call                               */
+} fdlp_mfcc_config;
+typedef struct fdlp_mfcc_plan fdlp_mfcc_plan;
+int fdlp_mfcc_plan_create(const fdlp_mfcc_config* cfg, int device, fdlp_mfcc_plan** out);
+int fdlp_mfcc_plan_destroy(fdlp_mfcc_plan* plan);
+/* F frames of an utterance of T samples (getFrames, features.py:151) and the output width
+ * min(13, nfilters) * (2 context + 1) (width may be NULL). */
+int fdlp_mfcc_geometry(const fdlp_mfcc_plan* plan, int64_t T, int32_t* F, int32_t* width);
+/* A batch (fdlp_batch as for fdlp_mel_compute: pcm int16 or float64 in the WAV's own scale, offsets, lengths,
+ * optional int16 noise mixing, out [sum F, width] at out_row, optional fp64 copy, ark_decimals).  `preprocess`
+ * must be FDLP_PRE_NONE; `jitter` and the compact-code fields are unused.  FDLP_E_CAPACITY past max_frames. */
+int fdlp_mfcc_compute(fdlp_mfcc_plan* plan, const fdlp_batch* batch, void* stream);
+/* Host-only view of the plan's tables (works on a device = -1 plan).  dims[8] = {n, nb, K, Kpad, nbpad, ncep,
+ * nfilters, frames per workgroup tile}; fold [nfilters, nb] (fb[m,k] + fb[m,n-k]), tw [Kpad, 2 nbpad]
+ * (cos | -sin of 2 pi ((i k) mod n) / n, zero padded), dct [nfilters, ncep].  Any of the three may be NULL. */
+int fdlp_mfcc_plan_tables(const fdlp_mfcc_plan* plan, int32_t* dims, double* fold, double* tw, double* dct);
+
 /* ---- augmentation: addReverb (features.py:110-115) -------------------------------------- */
 /* --add_reverb small_room|medium_room|large_room (computeFDLPSpectrogram.py:75-91, :168-170): after the
  * optional diff / noise preprocessing, every utterance is convolved with the RIR (channel 1 of
@@ -348,6 +380,12 @@ enum { FDLP_SIG_U8 = 1, FDLP_SIG_I16 = 2, FDLP_SIG_I32 = 3, FDLP_SIG_I64 = 4, FD
  * features.py:27.  The noise is int16 (noises/<name>.wav of the recipes). */
 int fdlp_noise_params_any(const double* sig, int64_t T, int32_t sig_kind, const int16_t* noise,
                           int64_t noise_len, double snr, double u, int64_t* off, double* alpha);
+
+/* computeMfccFeatures.py's own add_noise_to_wav (:48-55): signal and noise are divided by 2^15 into float64
+ * before the energies are taken, so no square wraps (unlike the two functions above).  `sig` holds the WAV's
+ * unscaled sample values; the exact 2^-15 scaling cancels in alpha. */
+int fdlp_noise_params_f64(const double* sig, int64_t T, const int16_t* noise, int64_t noise_len,
+                          double snr, double u, int64_t* off, double* alpha);
 
 /* ---- native I/O (replaces scipy.io.wavfile.read :139 and dict2Ark + copy-feats :231) ---- */
 /* Parse a RIFF/WAVE PCM16 mono buffer.  *samples points into `buf`. */

@@ -84,6 +84,13 @@ class FdlpMelConfigC(ctypes.Structure):
     ]
 
 
+class FdlpMfccConfigC(ctypes.Structure):
+    _fields_ = [
+        ("nfilters", c_i32), ("nfft", c_i32), ("frate", c_i32), ("srate", c_i32), ("fduration", c_dbl),
+        ("context", c_i32), ("max_frames", c_i32),
+    ]
+
+
 class FdlpReverbBatchC(ctypes.Structure):
     _fields_ = [
         ("n_utt", c_i32), ("pcm_kind", c_i32), ("pcm_dev", c_p), ("pcm_off", P_i64), ("utt_len", P_i64),
@@ -173,6 +180,12 @@ SIGNATURES = {
     "fdlp_mel_plan_destroy": (c_i32, [c_p]),
     "fdlp_mel_geometry": (c_i32, [c_p, c_i64, P_i32]),
     "fdlp_mel_compute": (c_i32, [c_p, ctypes.POINTER(FdlpBatchC), c_p]),
+    "fdlp_mfcc_plan_create": (c_i32, [ctypes.POINTER(FdlpMfccConfigC), c_i32, ctypes.POINTER(c_p)]),
+    "fdlp_mfcc_plan_destroy": (c_i32, [c_p]),
+    "fdlp_mfcc_geometry": (c_i32, [c_p, c_i64, P_i32, P_i32]),
+    "fdlp_mfcc_compute": (c_i32, [c_p, ctypes.POINTER(FdlpBatchC), c_p]),
+    "fdlp_mfcc_plan_tables": (c_i32, [c_p, P_i32, P_dbl, P_dbl, P_dbl]),
+    "fdlp_noise_params_f64": (c_i32, [P_dbl, c_i64, P_i16, c_i64, c_dbl, c_dbl, P_i64, P_dbl]),
     "fdlp_mat_reader_open": (c_i32, [ctypes.c_char_p, ctypes.POINTER(c_p)]),
     "fdlp_mat_reader_next": (c_i32, [c_p, ctypes.POINTER(ctypes.c_char_p), P_i32, P_i32,
                                      ctypes.POINTER(ctypes.POINTER(ctypes.c_float))]),

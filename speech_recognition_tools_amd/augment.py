@@ -42,6 +42,21 @@ def noise_params(sig: np.ndarray, noise: np.ndarray, snr: float, u: float, kind:
     return off.value, alpha.value
 
 
+def noise_params_f64(sig: np.ndarray, noise: np.ndarray, snr: float, u: float):
+    """(offset, alpha) of computeMfccFeatures.py's own add_noise_to_wav (:48-55) for the uniform draw u: that
+    script divides signal and noise by 2**15 into float64 first, so neither energy wraps.  `sig` and `noise`
+    hold the WAVs' unscaled samples (the exact scaling cancels in alpha)."""
+    if noise.dtype != np.int16:
+        raise NotImplementedError("noise files other than 16-bit PCM (the recipes' noises/*.wav are 16-bit)")
+    n = np.ascontiguousarray(noise, dtype=np.int16)
+    s = np.ascontiguousarray(np.asarray(sig), dtype=np.float64)
+    off = ctypes.c_int64()
+    alpha = ctypes.c_double()
+    check(lib.fdlp_noise_params_f64(ptr(s, ctypes.c_double), s.size, ptr(n, ctypes.c_int16), n.size, float(snr),
+                                    float(u), ctypes.byref(off), ctypes.byref(alpha)))
+    return off.value, alpha.value
+
+
 ROOMS = {  # computeFDLPSpectrogram.py:75-87 (the reference's relative ./RIR paths)
     "small_room": "./RIR/RIR_SmallRoom1_near_AnglA.wav",
     "medium_room": "./RIR/RIR_MediumRoom1_far_AnglA.wav",

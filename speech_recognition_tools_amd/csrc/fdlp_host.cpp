@@ -245,6 +245,24 @@ int fdlp_noise_params_any(const double* sig, int64_t T, int32_t kind, const int1
   return FDLP_OK;
 }
 
+// computeMfccFeatures.py's own add_noise_to_wav (:48-55): signal and noise are float64 (x / 2^15) before the
+// energies are taken, so nothing wraps.  The 2^-15 scaling is exact and cancels in E_s / E_n, so alpha is
+// computed on the unscaled values; the sums follow np.mean's pairwise order.
+int fdlp_noise_params_f64(const double* sig, int64_t T, const int16_t* noise, int64_t noise_len, double snr,
+                          double u, int64_t* off, double* alpha) {
+  if (!sig || !noise || !off || !alpha || T <= 0) return fdlp::fail(FDLP_E_INVALID, "fdlp_noise_params_f64: bad args");
+  const double span = (double)(noise_len - T);  // :49
+  const int64_t o = (int64_t)floor(u * span);
+  if (o < 0 || o + T > noise_len)
+    return fdlp::fail(FDLP_E_INVALID, "noise file shorter than the utterance (reference slices a short noise)");
+  std::vector<double> nz((size_t)T);
+  for (int64_t t = 0; t < T; ++t) nz[(size_t)t] = (double)noise[o + t];
+  const double Es = np_mean_square(sig, T, FDLP_SIG_F64), En = np_mean_square(nz.data(), T, FDLP_SIG_F64);
+  *alpha = sqrt(Es / (En * pow(10.0, snr / 10.0)));  // :53
+  *off = o;
+  return FDLP_OK;
+}
+
 // Compact ark codes -> the float32 ark values (fdlp_batch.out_q_dev, fdlp_device.h q_code): the device
 // stores (float)(k / 10^d) in out_dev; here the same two IEEE operations on the same k, so the floats
 // are bitwise the ones the device would have written.  -32768 is -0.0.  The 65536 values of a decimals

@@ -200,6 +200,28 @@ hipError_t launch_mel(const MelConsts& c, const MelFrame* frames, int nframes, c
                       const int16_t* noise, float* out, double* out64, int decimals, hipStream_t s);
 size_t mel_lds_bytes(int nh);
 
+// MFCC (computeMfccFeatures.py): one analysis frame and the plan constants (fdlp_mfcc.hip).
+struct MfccFrame {
+  int64_t pcm_off, noise_off;  // noise_off < 0: no mixing
+  double alpha;
+  int64_t out_row;
+  int32_t T, k, F, pad_;       // utterance samples, frame index in the utterance, its frame count
+};
+struct MfccConsts {
+  int L, hop, ext, n, nb, K, Kpad, nbpad, nfilters, ncep, context, rt;
+  const double* window;  // [L]  np.hamming(L)
+  const double* tw;      // [Kpad, 2 nbpad]  cos | -sin of 2 pi ((i k) mod n) / n, zero padded
+  const double* fold;    // [nfilters, nb]   filterbank with the mirrored bins folded in
+  const int* lo;         // [nfilters] first non-zero tap of fold
+  const int* hi;         // [nfilters] one past the last
+  const double* dct;     // [nfilters, ncep] 2 cos(pi q (2m+1) / (2 nfilters))
+};
+// cep: [nframes, ncep] fp64 scratch, used when c.context > 0
+hipError_t launch_mfcc(const MfccConsts& c, const MfccFrame* frames, int nframes, const void* pcm, int pcm_kind,
+                       const int16_t* noise, double* cep, float* out, double* out64, int decimals, hipStream_t s);
+size_t mfcc_lds_bytes(int rt, int Kpad, int nbpad, int nfilters);
+int mfcc_row_tiles(int Kpad, int nbpad, int nfilters);  // 16-frame row tiles per workgroup (2, 1; 0 = too large)
+
 // One utterance of a reverb batch (fdlp_reverb): samples at pcm[off, off+T), y at [yoff, yoff+T+R-1).
 struct RevUtt {
   int64_t off, T, yoff, noff;  // noff < 0: no noise mixing

@@ -1515,6 +1515,201 @@ int fdlp_mel_compute(fdlp_mel_plan* p, const fdlp_batch* b, void* stream) {
   return FDLP_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// MFCC plan (computeMfccFeatures.py:58-135, fdlp_mfcc.hip)
+// ---------------------------------------------------------------------------------------------
+struct fdlp_mfcc_plan {
+  fdlp_mfcc_config cfg{};
+  int device = 0;
+  int L = 0, hop = 0, sp_b = 0, sp_f = 0, ext = 0;
+  int n = 0, nb = 0, K = 0, Kpad = 0, nbpad = 0, ncep = 0, width = 0, rt = 0;
+  std::vector<double> fold, tw, dct;  // host copies (fdlp_mfcc_plan_tables)
+  fdlp::MfccConsts mc{};
+  double *d_win = nullptr, *d_fold = nullptr, *d_tw = nullptr, *d_dct = nullptr, *d_cep = nullptr;
+  int *d_lo = nullptr, *d_hi = nullptr;
+  fdlp::MfccFrame* d_frames = nullptr;
+  fdlp::MfccFrame* h_frames = nullptr;  // pinned staging
+  hipEvent_t staging_done = nullptr;
+  bool staging_pending = false;
+};
+
+static int free_mfcc_plan(fdlp_mfcc_plan* p) {
+  if (!p) return FDLP_OK;
+  void* devs[] = {p->d_win, p->d_fold, p->d_tw, p->d_dct, p->d_cep, p->d_lo, p->d_hi, p->d_frames};
+  for (void* d : devs)
+    if (d) (void)hipFree(d);
+  if (p->h_frames) (void)hipHostFree(p->h_frames);
+  if (p->staging_done) (void)hipEventDestroy(p->staging_done);
+  delete p;
+  return FDLP_OK;
+}
+
+static int64_t mfcc_frames_of(const fdlp_mfcc_plan* p, int64_t T) {
+  const int64_t lim = T + 2 * (int64_t)p->ext - p->sp_b - p->sp_f;  // getFrames: k*hop < lim
+  if (lim <= 0) return 0;
+  return (lim - 1) / p->hop + 1;
+}
+
+int fdlp_mfcc_plan_create(const fdlp_mfcc_config* cfg, int device, fdlp_mfcc_plan** out) {
+  if (!cfg || !out) return fail(FDLP_E_INVALID, "fdlp_mfcc_plan_create: null argument");
+  *out = nullptr;
+  const fdlp_mfcc_config& c = *cfg;
+  if (c.nfilters < 1 || c.srate < 1 || c.frate < 1 || !(c.fduration > 0) || c.max_frames < 1 || c.context < 0)
+    return fail(FDLP_E_INVALID, "invalid mfcc configuration");
+  if (c.nfft < 2 || c.nfft % 2 || c.nfft > 65536) return fail(FDLP_E_INVALID, "nfft must be even and <= 65536");
+  auto* p = new (std::nothrow) fdlp_mfcc_plan;
+  if (!p) return fail(FDLP_E_NOMEM, "out of memory");
+  p->cfg = c;
+  p->device = device;
+  int rc;
+#define MFCC_FAIL(code, msg) do { rc = fail(code, msg); free_mfcc_plan(p); return rc; } while (0)
+#define MFCC_TRY(expr) do { rc = (expr); if (rc != FDLP_OK) { std::string m_ = fdlp::last_error_slot(); free_mfcc_plan(p); fdlp::last_error_slot() = m_; return rc; } } while (0)
+  p->L = (int)((double)c.srate * c.fduration);       // features.py:134
+  p->hop = (int)((double)c.srate / (double)c.frate);  // features.py:135
+  if (p->L % 2 == 0) { p->sp_b = p->L / 2 - 1; p->sp_f = p->L / 2; p->ext = p->L / 2 - 1; }
+  else { p->sp_b = p->sp_f = p->ext = (p->L - 1) / 2; }
+  if (p->L < 2 || p->hop < 1) MFCC_FAIL(FDLP_E_INVALID, "frame length / hop too small");
+  const int n = c.nfft / 2 + 1;  // fft(time_frames, int(nfft / 2 + 1))                  (:126)
+  const int nb = n / 2 + 1;      // real input: bins n-k mirror bins k
+  const int K = std::min(p->L, n);
+  p->n = n; p->nb = nb; p->K = K;
+  p->Kpad = (K + 3) / 4 * 4;
+  p->nbpad = (nb + 15) / 16 * 16;
+  p->ncep = std::min(13, c.nfilters);  // dct(...)[:, 0:13]                              (:127-128)
+  p->width = p->ncep * (2 * c.context + 1);
+  p->rt = fdlp::mfcc_row_tiles(p->Kpad, p->nbpad, c.nfilters);
+  if (p->rt == 0)
+    MFCC_FAIL(FDLP_E_INVALID, "mfcc tile exceeds the 160 KB LDS: need max(min(L, n), nfilters) + n/2 <= ~1230 "
+                              "(n = nfft/2 + 1, L = srate * fduration)");
+  int ncol = 0;
+  const std::vector<double> fb = fbank_mel(c.nfilters, c.nfft, c.srate, 1.0, &ncol);  // createFbank   (:74)
+  if (ncol != n) MFCC_FAIL(FDLP_E_INVALID, "filterbank width does not match nfft/2+1");
+  // |X[n-k]| = |X[k]|: the mirrored columns fold onto bins 1 .. nb-1 (not onto the Nyquist bin of an even n)
+  p->fold.assign((size_t)c.nfilters * nb, 0.0);
+  for (int m = 0; m < c.nfilters; ++m)
+    for (int k = 0; k < nb; ++k) {
+      double v = fb[(size_t)m * n + k];
+      if (k >= 1 && n - k != k) v += fb[(size_t)m * n + (n - k)];
+      p->fold[(size_t)m * nb + k] = v;
+    }
+  std::vector<int> lo(c.nfilters, 0), hi(c.nfilters, 0);
+  for (int m = 0; m < c.nfilters; ++m) {
+    int a = nb, b = 0;
+    for (int k = 0; k < nb; ++k)
+      if (p->fold[(size_t)m * nb + k] != 0.0) { a = std::min(a, k); b = k + 1; }
+    if (b <= a) { a = 0; b = 0; }
+    lo[m] = a;
+    hi[m] = b;
+  }
+  const std::vector<double> win = cos_window(p->L, 0.54, 0.46);  // np.hamming (:59)
+  const long double PI = 3.141592653589793238462643383279502884L;
+  // twiddles on the integer-reduced argument (i k) mod n, in long double
+  const size_t ld = 2 * (size_t)p->nbpad;
+  p->tw.assign((size_t)p->Kpad * ld, 0.0);
+  for (int i = 0; i < K; ++i)
+    for (int k = 0; k < nb; ++k) {
+      const int64_t r = ((int64_t)i * k) % n;
+      const long double ang = 2.0L * PI * (long double)r / (long double)n;
+      p->tw[(size_t)i * ld + k] = (double)cosl(ang);
+      p->tw[(size_t)i * ld + p->nbpad + k] = (double)-sinl(ang);
+    }
+  // scipy.fftpack.dct type 2, unnormalised: y[q] = 2 sum_m x[m] cos(pi q (2m+1) / (2 N))
+  p->dct.assign((size_t)c.nfilters * p->ncep, 0.0);
+  for (int m = 0; m < c.nfilters; ++m)
+    for (int q = 0; q < p->ncep; ++q) {
+      const int64_t r = ((int64_t)q * (2 * m + 1)) % (4 * (int64_t)c.nfilters);
+      p->dct[(size_t)m * p->ncep + q] = (double)(2.0L * cosl(PI * (long double)r / (long double)(2 * c.nfilters)));
+    }
+  if (device < 0) {
+    *out = p;
+    return FDLP_OK;
+  }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) MFCC_FAIL(FDLP_E_HIP, "no HIP device visible");
+  if (device >= ndev) MFCC_FAIL(FDLP_E_INVALID, "device index out of range");
+  DeviceGuard dg(device);
+  if (dg.status() != hipSuccess) MFCC_FAIL(FDLP_E_HIP, "hipSetDevice failed");
+  MFCC_TRY(upload(&p->d_win, win.data(), win.size()));
+  MFCC_TRY(upload(&p->d_fold, p->fold.data(), p->fold.size()));
+  MFCC_TRY(upload(&p->d_tw, p->tw.data(), p->tw.size()));
+  MFCC_TRY(upload(&p->d_dct, p->dct.data(), p->dct.size()));
+  MFCC_TRY(upload(&p->d_lo, lo.data(), lo.size()));
+  MFCC_TRY(upload(&p->d_hi, hi.data(), hi.size()));
+  if (hipMalloc((void**)&p->d_frames, sizeof(fdlp::MfccFrame) * c.max_frames) != hipSuccess ||
+      hipHostMalloc((void**)&p->h_frames, sizeof(fdlp::MfccFrame) * c.max_frames, hipHostMallocDefault) != hipSuccess ||
+      (c.context > 0 && hipMalloc((void**)&p->d_cep, sizeof(double) * (size_t)c.max_frames * p->ncep) != hipSuccess) ||
+      hipEventCreateWithFlags(&p->staging_done, hipEventDisableTiming) != hipSuccess)
+    MFCC_FAIL(FDLP_E_NOMEM, "mfcc plan workspace allocation failed");
+  fdlp::MfccConsts& m = p->mc;
+  m.L = p->L; m.hop = p->hop; m.ext = p->ext; m.n = n; m.nb = nb; m.K = K; m.Kpad = p->Kpad; m.nbpad = p->nbpad;
+  m.nfilters = c.nfilters; m.ncep = p->ncep; m.context = c.context; m.rt = p->rt;
+  m.window = p->d_win; m.tw = p->d_tw; m.fold = p->d_fold; m.lo = p->d_lo; m.hi = p->d_hi; m.dct = p->d_dct;
+#undef MFCC_FAIL
+#undef MFCC_TRY
+  *out = p;
+  return FDLP_OK;
+}
+
+int fdlp_mfcc_plan_destroy(fdlp_mfcc_plan* p) { return free_mfcc_plan(p); }
+
+int fdlp_mfcc_geometry(const fdlp_mfcc_plan* p, int64_t T, int32_t* F, int32_t* width) {
+  if (!p || !F || T < 0) return fail(FDLP_E_INVALID, "fdlp_mfcc_geometry: bad args");
+  *F = (int32_t)mfcc_frames_of(p, T);
+  if (width) *width = p->width;
+  return FDLP_OK;
+}
+
+int fdlp_mfcc_plan_tables(const fdlp_mfcc_plan* p, int32_t* dims, double* fold, double* tw, double* dct) {
+  if (!p || !dims) return fail(FDLP_E_INVALID, "fdlp_mfcc_plan_tables: bad args");
+  const int32_t d[8] = {p->n, p->nb, p->K, p->Kpad, p->nbpad, p->ncep, p->cfg.nfilters, 16 * p->rt};
+  memcpy(dims, d, sizeof(d));
+  if (fold) memcpy(fold, p->fold.data(), sizeof(double) * p->fold.size());
+  if (tw) memcpy(tw, p->tw.data(), sizeof(double) * p->tw.size());
+  if (dct) memcpy(dct, p->dct.data(), sizeof(double) * p->dct.size());
+  return FDLP_OK;
+}
+
+int fdlp_mfcc_compute(fdlp_mfcc_plan* p, const fdlp_batch* b, void* stream) {
+  if (!p || !b || p->device < 0) return fail(FDLP_E_INVALID, "fdlp_mfcc_compute: bad args or host-only plan");
+  if (b->n_utt < 0 || (b->n_utt > 0 && (!b->pcm_dev || !b->pcm_off || !b->utt_len || !b->out_row)) ||
+      (!b->out_dev && !b->out_f64_dev))
+    return fail(FDLP_E_INVALID, "fdlp_mfcc_compute: bad batch");
+  if (b->pcm_kind != FDLP_PCM_I16 && b->pcm_kind != FDLP_PCM_F64) return fail(FDLP_E_INVALID, "unknown pcm_kind");
+  if (b->noise_dev && (!b->noise_off || !b->noise_alpha || b->pcm_kind != FDLP_PCM_I16))
+    return fail(FDLP_E_INVALID, "noise mixing needs int16 PCM and the noise arrays");
+  if (b->preprocess != FDLP_PRE_NONE) return fail(FDLP_E_INVALID, "computeMfccFeatures.py has no diff preprocessing");
+  hipStream_t s = (hipStream_t)stream;
+  if (p->staging_pending) {
+    HIP_TRY(hipEventSynchronize(p->staging_done));
+    p->staging_pending = false;
+  }
+  int nf = 0;
+  for (int u = 0; u < b->n_utt; ++u) {
+    const int64_t T = b->utt_len[u];
+    if (T < 1 || T > INT32_MAX || b->pcm_off[u] < 0) return fail(FDLP_E_INVALID, "empty or oversized utterance");
+    const int64_t F = mfcc_frames_of(p, T);
+    if (nf + F > p->cfg.max_frames) return fail(FDLP_E_CAPACITY, "batch exceeds the mfcc plan's max_frames");
+    for (int64_t k = 0; k < F; ++k) {
+      fdlp::MfccFrame& fd = p->h_frames[nf++];
+      fd.pcm_off = b->pcm_off[u];
+      fd.noise_off = b->noise_dev ? b->noise_off[u] : -1;
+      fd.alpha = b->noise_dev ? b->noise_alpha[u] : 0.0;
+      fd.out_row = b->out_row[u] + k;
+      fd.T = (int32_t)T;
+      fd.k = (int32_t)k;
+      fd.F = (int32_t)F;
+      fd.pad_ = 0;
+    }
+  }
+  if (nf == 0) return FDLP_OK;
+  HIP_TRY(hipMemcpyAsync(p->d_frames, p->h_frames, sizeof(fdlp::MfccFrame) * nf, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipEventRecord(p->staging_done, s));
+  p->staging_pending = true;
+  HIP_TRY(fdlp::launch_mfcc(p->mc, p->d_frames, nf, b->pcm_dev, b->pcm_kind, b->noise_dev, p->d_cep, b->out_dev,
+                            b->out_f64_dev, b->ark_decimals, s));
+  return FDLP_OK;
+}
+
 int fdlp_reverb(const fdlp_reverb_batch* b, void* stream) {
   if (!b || b->n_utt < 0 || !b->pcm_off || !b->utt_len || !b->rir_dev || b->rir_len < 1 || !b->out_dev ||
       !b->out_len || (b->n_utt > 0 && !b->pcm_dev) || (b->noise_dev && (!b->noise_off || !b->noise_alpha)) ||

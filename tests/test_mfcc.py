@@ -1,0 +1,338 @@
+"""MFCC baseline feature: src/featgen/computeMfccFeatures.py (compute-mfcc-feats, MfccPlan, mfcc_kernel).
+
+CPU (device = -1 plans): argparse surface, geometry, the plan's tables (twiddles, folded filterbank, DCT matrix)
+and a numpy evaluation of the reference chain built from those tables against the real reference's outputs
+(tests/golden/mfcc_*.npz, made by tests/golden/make_golden_mfcc.py), the non-wrapping noise parameters, and
+the configurations the plan refuses.
+GPU: every golden set through MfccPlan.compute at atol 1e-6 (the bar test_melspec.py holds the mel kernel to
+is tighter; the CPU formulation's own error is ~1e-13), the '%.3f' rounding, tiling invariance, context
+splicing across utterance ends, float64 PCM input, and the CLI in a child process."""
+import json
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from conftest import GOLDEN, ROOT, load_golden
+from oracle import fdlp_oracle as O
+from oracle import mel_oracle as MO
+
+MFCC_SETS = ["mfcc_default", "mfcc_context", "mfcc_trunc", "mfcc_even_n", "mfcc_noise_reverb"]
+FDLP_E_INVALID = -1
+
+
+def _cfg(meta, **over):
+    from speech_recognition_tools_amd.mfcc import MfccConfig
+    o = dict(meta["opts"], **over)
+    return MfccConfig(nfilters=o["nfilters"], fduration=o["fduration"], frate=o["frate"], nfft=o["nfft"],
+                      context=o["context"])
+
+
+def _create_fbank(nfilters, nfft, srate):
+    """features.py createFbank (:172-190) restated."""
+    mel_max = 2595 * np.log10(1 + srate / 1400)
+    fw = np.linspace(0, mel_max, nfilters + 2)
+    fb = np.zeros((nfilters, int(np.floor(nfft / 2 + 1))))
+    edge = np.floor((nfft + 1) * (700 * (10 ** (fw / 2595) - 1)) / srate)
+    for m in range(1, nfilters + 1):
+        l, c, r = int(edge[m - 1]), int(edge[m]), int(edge[m + 1])
+        for k in range(l, c):
+            fb[m - 1, k] = (k - edge[m - 1]) / (edge[m] - edge[m - 1])
+        for k in range(c, r):
+            fb[m - 1, k] = (edge[m + 1] - k) / (edge[m + 1] - edge[m])
+    return fb
+
+
+def _splice(feats, C):
+    """features.py spliceFeats (:157-169): rows F-C .. F-1 stay zero."""
+    F, D = feats.shape
+    out = np.zeros((F, D * (2 * C + 1)))
+    pad = np.concatenate([np.zeros((C, D)), feats, np.zeros((C, D))])
+    for i in range(0, F - C):
+        out[i] = pad[i:i + 2 * C + 1].reshape(-1)
+    return out
+
+
+def _noise_f64(sig, noise, snr, u):
+    """computeMfccFeatures.py add_noise_to_wav (:48-55) on the / 2**15 float64 arrays."""
+    s, n = sig / np.power(2, 15), noise / np.power(2, 15)
+    off = int(np.floor(u * (len(n) - len(s))))
+    ns = n[off:off + len(s)]
+    alp = np.sqrt(np.mean(s ** 2) / (np.mean(ns ** 2) * (10 ** (snr / 10))))
+    return off, alp, s + alp * ns
+
+
+def _reference_inputs(meta, sig, z):
+    """The float64 signals entering getFrames, as the reference loop makes them (:113-120)."""
+    o = meta["opts"]
+    rng = np.random.RandomState(meta["extra"]["noise_seed"]) if "noise_seed" in meta["extra"] else None
+    out = {}
+    for u in meta["utts"]:
+        x = sig[u] / np.power(2, 15)
+        if o["add_noise"] != "none":
+            x = _noise_f64(sig[u], z["noise_babble"], float(o["add_noise"].split(",")[1]), rng.rand())[2]
+        if o["add_reverb"] not in (None, "clean"):
+            x = O.add_reverb(x, O.load_rir(z["rir"]))
+        out[u] = x
+    return out
+
+
+def test_mfcc_cli_argparse_surface_matches_reference():
+    from speech_recognition_tools_amd.featgen import computeMfccFeatures as cm
+    ref = json.load(open(os.path.join(GOLDEN, "cli_options_mfcc.json")))
+    assert [o["name"] for o in ref][:2] == ["scp", "outfile"] and len(ref) == 10
+    args = cm.get_args(["a.scp", "out"])
+    for o in ref:
+        dest = o["name"].lstrip("-")
+        assert hasattr(args, dest), o
+        if dest not in ("scp", "outfile"):
+            assert getattr(args, dest) == o.get("default"), o
+    assert args.add_noise == "none" and args.context is None and args.kaldi_cmd is None
+    a = cm.get_args(["a.scp", "out", "--context=3", "--nfft=512", "--fduration=0.025", "--nfilters=8", "--frate=50"])
+    for o in ref:
+        if "type" in o:
+            assert type(getattr(a, o["name"].lstrip("-"))).__name__ == o["type"], o
+    for extra in ("noise_seed", "device", "batch_frames", "io_workers", "ark_precision"):
+        assert hasattr(args, extra)
+
+
+def test_mfcc_geometry_and_width():
+    from speech_recognition_tools_amd.mfcc import MfccConfig, MfccPlan
+    for fd, fr, ctx, nf, width in ((0.02, 100, None, 30, 13), (0.025, 100, 3, 30, 91), (0.02, 100, 1, 8, 24),
+                                   (0.02, 100, 0, 5, 5)):
+        plan = MfccPlan(MfccConfig(fduration=fd, frate=fr, context=ctx, nfilters=nf), device=-1)
+        assert plan.width == width
+        for T in (2, 5, 160, 161, 319, 320, 321, 4000):
+            assert plan.frames(T) == MO.get_frames(np.zeros(T), 16000, fr, fd).shape[0], (fd, fr, T)
+    for name in MFCC_SETS:
+        meta, sig, ref, _ = load_golden(name)
+        plan = MfccPlan(_cfg(meta), device=-1)
+        for u in meta["utts"]:
+            # reverb keeps the length here (the best shift is not the last one)
+            assert (plan.frames(sig[u].size), plan.width) == ref[u].shape, (name, u)
+
+
+@pytest.mark.parametrize("name", MFCC_SETS)
+def test_mfcc_tables_and_cpu_chain_match_reference(name):
+    from speech_recognition_tools_amd.mfcc import MfccPlan
+    meta, sig, ref, z = load_golden(name)
+    o = meta["opts"]
+    t = MfccPlan(_cfg(meta), device=-1).tables()
+    L = int(16000 * o["fduration"])
+    n, nb, K, nf = t["n"], t["nb"], t["K"], o["nfilters"]
+    assert (n, nb, K, t["ncep"]) == (o["nfft"] // 2 + 1, (o["nfft"] // 2 + 1) // 2 + 1, min(L, n), min(13, nf))
+    assert t["Kpad"] % 4 == 0 and t["Kpad"] >= K and t["nbpad"] % 16 == 0 and t["nbpad"] >= nb
+    assert t["tile"] in (16, 32)
+    # twiddles: cos | -sin of 2 pi ((i k) mod n) / n, in extended precision
+    ld = np.longdouble
+    assert np.finfo(ld).eps < 1e-18
+    r = (np.arange(K)[:, None] * np.arange(nb)[None, :]) % n
+    ang = 8 * np.arctan(ld(1)) * r.astype(ld) / ld(n)
+    tw = t["tw"]
+    assert np.abs(tw[:K, :nb].astype(ld) - np.cos(ang)).max() <= 2e-16
+    assert np.abs(tw[:K, t["nbpad"]:t["nbpad"] + nb].astype(ld) + np.sin(ang)).max() <= 2e-16
+    assert not tw[K:].any() and not tw[:, nb:t["nbpad"]].any() and not tw[:, t["nbpad"] + nb:].any()
+    # folded filterbank
+    fb = _create_fbank(nf, o["nfft"], 16000)
+    assert fb.shape[1] == n
+    fold = fb[:, :nb].copy()
+    for k in range(1, nb):
+        if n - k != k:
+            fold[:, k] += fb[:, n - k]
+    np.testing.assert_array_equal(t["fold"], fold)
+    # DCT-II matrix, unnormalised
+    m, q = np.arange(nf)[:, None], np.arange(t["ncep"])[None, :]
+    dct = 2 * np.cos(4 * np.arctan(ld(1)) * (q * (2 * m + 1)).astype(ld) / ld(2 * nf))
+    assert np.abs(t["dct"].astype(ld) - dct).max() <= 1e-15
+    # the reference chain evaluated with these tables
+    xs = _reference_inputs(meta, sig, z)
+    for u in meta["utts"]:
+        fr = MO.get_frames(xs[u], 16000, o["frate"], o["fduration"])[:, :K]
+        re = fr @ tw[:K, :nb]
+        im = fr @ tw[:K, t["nbpad"]:t["nbpad"] + nb]
+        mfcc = np.log10(np.hypot(re, im) @ t["fold"].T) @ t["dct"]
+        if o["context"]:
+            mfcc = _splice(mfcc, o["context"])
+        assert mfcc.shape == ref[u].shape, u
+        assert np.isfinite(ref[u]).all()
+        np.testing.assert_allclose(mfcc, ref[u], rtol=0, atol=1e-10)
+
+
+def test_mfcc_noise_params_do_not_wrap():
+    from speech_recognition_tools_amd import NpRandom
+    from speech_recognition_tools_amd.augment import noise_params, noise_params_f64
+    meta, sig, _, z = load_golden("mfcc_noise_reverb")
+    noise = z["noise_babble"]
+    snr = float(meta["opts"]["add_noise"].split(",")[1])
+    ours, ref = NpRandom(meta["extra"]["noise_seed"]), np.random.RandomState(meta["extra"]["noise_seed"])
+    for u in meta["utts"]:
+        draw = ours.rand()
+        assert draw == ref.rand()
+        off, alp = noise_params_f64(sig[u], noise, snr, draw)
+        off2, alp2, _ = _noise_f64(sig[u], noise, snr, draw)
+        assert off == off2
+        np.testing.assert_equal(alp, alp2)
+        assert alp != noise_params(sig[u], noise, snr, draw)[1]  # the int16-wrapping energies of features.py
+        # float64 samples (any non-16-bit WAV) take the same route
+        assert noise_params_f64(sig[u].astype(np.float64), noise, snr, draw) == (off, alp)
+
+
+@pytest.mark.parametrize("bad", [dict(nfft=1023), dict(nfilters=0), dict(max_frames=0)])
+def test_mfcc_plan_rejects_bad_configurations(bad):
+    from speech_recognition_tools_amd import FdlpError
+    from speech_recognition_tools_amd.mfcc import MfccConfig, MfccPlan
+    bad = dict(bad)
+    mf = bad.pop("max_frames", 64)
+    with pytest.raises(FdlpError) as e:
+        MfccPlan(MfccConfig(**bad), device=-1, max_frames=mf)
+    assert e.value.code == FDLP_E_INVALID
+
+
+def test_mfcc_plan_states_its_size_limit():
+    from speech_recognition_tools_amd import FdlpError
+    from speech_recognition_tools_amd.mfcc import MfccConfig, MfccPlan
+    assert MfccPlan(MfccConfig(nfft=2048), device=-1).tables()["tile"] == 16
+    with pytest.raises(FdlpError, match="LDS") as e:
+        MfccPlan(MfccConfig(nfft=8192), device=-1)
+    assert e.value.code == FDLP_E_INVALID
+
+
+# ---------------------------------------------------------------------------------------------------------
+# GPU
+# ---------------------------------------------------------------------------------------------------------
+def _mfcc_gpu(meta, sig, z, utts=None, as_f64=False, plan=None):
+    """{utt: (out64, out)} of one MfccPlan.compute call over `utts` (noise / reverb as the CLI routes them)."""
+    import torch
+    from speech_recognition_tools_amd import NpRandom
+    from speech_recognition_tools_amd.augment import noise_params_f64, reverb
+    from speech_recognition_tools_amd.mfcc import MfccPlan
+    plan = plan or MfccPlan(_cfg(meta), device=0, max_frames=256)
+    utts = utts or meta["utts"]
+    lens = [sig[u].size for u in utts]
+    x = np.concatenate([sig[u] for u in utts])
+    pcm = torch.from_numpy(x.astype(np.float64) if as_f64 else x).cuda()
+    o = meta["opts"]
+    kw = {}
+    if o["add_noise"] != "none":
+        noise = z["noise_babble"]
+        nr = NpRandom(meta["extra"]["noise_seed"])
+        draws = {u: nr.rand() for u in meta["utts"]}
+        offs, alps = zip(*[noise_params_f64(sig[u], noise, float(o["add_noise"].split(",")[1]), draws[u])
+                           for u in utts])
+        kw = dict(noise=torch.from_numpy(noise).cuda(), noise_off=list(offs), noise_alpha=list(alps))
+    if o["add_reverb"] not in (None, "clean"):
+        pcm, lens = reverb(pcm, lens, torch.from_numpy(O.load_rir(z["rir"])).cuda(), **kw)
+        kw = {}
+    out, rows, out64 = plan.compute(pcm, lens, want_f64=True, **kw)
+    out, out64 = out.cpu().numpy(), out64.cpu().numpy()
+    return {u: (out64[rows[i]:rows[i + 1]], out[rows[i]:rows[i + 1]]) for i, u in enumerate(utts)}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", MFCC_SETS)
+def test_mfcc_gpu_vs_reference_golden(name):
+    meta, sig, ref, z = load_golden(name)
+    res = _mfcc_gpu(meta, sig, z)
+    worst = 0.0
+    for u in meta["utts"]:
+        f64, f32 = res[u]
+        assert f64.shape == ref[u].shape, u
+        worst = max(worst, float(np.abs(f64 - ref[u]).max()))
+        np.testing.assert_array_equal(f32, (np.rint(f64 * 1e3) / 1e3).astype(np.float32))
+    print("%s: max |out64 - reference| = %.3g" % (name, worst))
+    assert worst <= 1e-6, (name, worst)
+
+
+@pytest.mark.gpu
+def test_mfcc_tiling_invariance():
+    from speech_recognition_tools_amd.mfcc import MfccConfig, MfccPlan
+
+    def speech_like(T, seed):  # seeded, non-silent
+        return np.round(np.random.default_rng(seed).standard_normal(T) * 2000).astype(np.int16)
+
+    plan = MfccPlan(MfccConfig(), device=0, max_frames=256)
+    tile = plan.tables()["tile"]
+    frames = [tile - 12, tile + 5, 8]                       # 2 tiles + 1 frame; boundaries inside tiles
+    assert sum(frames) == 2 * tile + 1
+    sig = {"u%d" % i: speech_like(160 * (F - 1) + 50, 300 + i) for i, F in enumerate(frames)}
+    meta = dict(opts=dict(nfilters=30, fduration=0.02, frate=100, nfft=1024, context=None, add_noise="none",
+                          add_reverb=None), utts=list(sig))
+    assert [plan.frames(x.size) for x in sig.values()] == frames
+    whole = _mfcc_gpu(meta, sig, None, plan=plan)
+    split = dict(_mfcc_gpu(meta, sig, None, utts=["u0"], plan=plan))
+    split.update(_mfcc_gpu(meta, sig, None, utts=["u1", "u2"], plan=plan))
+    for u in sig:
+        alone = _mfcc_gpu(meta, sig, None, utts=[u], plan=plan)[u]
+        assert np.isfinite(whole[u][0]).all()
+        for other in (split[u], alone):
+            np.testing.assert_array_equal(whole[u][0], other[0])
+            np.testing.assert_array_equal(whole[u][1], other[1])
+
+
+@pytest.mark.gpu
+def test_mfcc_context_zero_rows_and_utterance_isolation():
+    meta, sig, ref, z = load_golden("mfcc_context")
+    C = meta["opts"]["context"]
+    both = _mfcc_gpu(meta, sig, z)
+    for u in meta["utts"]:
+        f64 = both[u][0]
+        F = f64.shape[0]
+        assert not f64[max(F - C, 0):].any(), u                              # rows F-C .. F-1 (all when F <= C)
+        assert np.abs(f64 - ref[u]).max() <= 1e-6, u
+        if F > C:
+            assert not f64[0, :13 * C].any() and f64[0, 13 * C:].all()       # zero padding before frame 0
+            # the last spliced row ends with frames F-C-1+1 .. F-1 of this utterance, not the neighbour's
+            plain = _mfcc_gpu(dict(meta, opts=dict(meta["opts"], context=None)), sig, z, utts=[u])[u][0]
+            np.testing.assert_array_equal(f64[F - C - 1], plain[F - 2 * C - 1:F].reshape(-1))
+        alone = _mfcc_gpu(meta, sig, z, utts=[u])[u]
+        np.testing.assert_array_equal(f64, alone[0])
+        np.testing.assert_array_equal(both[u][1], alone[1])
+    assert ref["x2"].shape[0] <= C and not ref["x2"].any()
+
+
+@pytest.mark.gpu
+def test_mfcc_float64_pcm_equals_int16():
+    meta, sig, ref, z = load_golden("mfcc_default")
+    a, b = _mfcc_gpu(meta, sig, z), _mfcc_gpu(meta, sig, z, as_f64=True)
+    for u in meta["utts"]:
+        np.testing.assert_array_equal(a[u][0], b[u][0])
+        np.testing.assert_array_equal(a[u][1], b[u][1])
+
+
+@pytest.mark.gpu
+def test_mfcc_capacity_is_refused():
+    import torch
+    from speech_recognition_tools_amd import FdlpError
+    from speech_recognition_tools_amd.mfcc import MfccConfig, MfccPlan
+    plan = MfccPlan(MfccConfig(), device=0, max_frames=4)
+    pcm = torch.ones(4000, dtype=torch.int16).cuda()
+    with pytest.raises(FdlpError, match="max_frames") as e:
+        plan.compute(pcm, [4000])
+    assert e.value.code == -4  # FDLP_E_CAPACITY
+
+
+@pytest.mark.gpu
+def test_mfcc_cli_writes_reference_arks(tmp_path):
+    from scipy.io import wavfile
+    from speech_recognition_tools_amd.featgen.features import read_ark
+    meta, sig, ref, z = load_golden("mfcc_default")
+    scp = tmp_path / "wav.scp"
+    with open(scp, "w") as f:
+        for u in meta["utts"]:
+            p = tmp_path / (u + ".wav")
+            wavfile.write(str(p), 16000, sig[u])
+            f.write("%s %s\n" % (u, p))
+    out = str(tmp_path / "mfcc")
+    env = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
+    r = subprocess.run([os.path.join(ROOT, "bin", "compute-mfcc-feats"), str(scp), out, "--kaldi_cmd=copy-feats"],
+                       cwd=str(tmp_path), env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300)
+    assert r.returncode == 0, r.stdout.decode("utf-8", "replace")
+    ark = read_ark(out + ".ark")
+    assert list(ark) == meta["utts"]
+    assert [l.split()[0] for l in open(out + ".scp")] == meta["utts"]
+    for u in meta["utts"]:
+        assert ark[u].shape == ref[u].shape
+        assert np.abs(ark[u] - ref[u]).max() <= 1.001e-3, u
+    assert not any(f.endswith(".tmp") for f in os.listdir(str(tmp_path)))
+    assert r.stdout.decode().count("Computing Features for file:") == len(meta["utts"])
