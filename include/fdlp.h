@@ -313,6 +313,62 @@ int fdlp_mfcc_compute(fdlp_mfcc_plan* plan, const fdlp_batch* batch, void* strea
  * (cos | -sin of 2 pi ((i k) mod n) / n, zero padded), dct [nfilters, ncep].  Any of the three may be NULL. */
 int fdlp_mfcc_plan_tables(const fdlp_mfcc_plan* plan, int32_t* dims, double* fold, double* tw, double* dct);
 
+/* ---- feature post-processing: apply-cmvn | add-deltas | splice-feats ------------------------ */
+/* The chain every consumer of the reference pipes the arks through (recipes/timit/local_pyspeech/decode.sh:84-90,
+ * get_Tandem_feats.sh:31-35, make_mfcc_feats.sh:108-118, src/nnet/data_prep_*.py), restated from Kaldi's
+ * documented behaviour (transform/cmvn.cc ApplyCmvn, feat/feature-functions.cc DeltaFeatures, SpliceFrames) and
+ * run as ONE kernel (fdlp_post.hip): each input row is read once per tile, each output row written once.
+ *   cmvn    y = fl32(fl32(x * scale[d]) + offset[d]); the multiply only when the batch sets norm_mul
+ *   deltas  block i of frame t = sum_j scales[i][j] * y[clamp(t + j, 0, T-1)], float32, ascending j, taps equal
+ *           to zero skipped; block 0 is y itself; columns [y | d | dd | ..] over the first `truncate` columns
+ *   splice  row t = rows clamp(t - L, 0, T-1) .. clamp(t + R, 0, T-1) of the above, concatenated
+ * A stage that is off (no norm table, delta_order 0, no context) is not executed. */
+typedef struct fdlp_post_config {
+  int32_t dim;            /* columns of the input rows                                        */
+  int32_t truncate;       /* add-deltas --truncate: keep the first n columns (0 = all)        */
+  int32_t delta_order;    /* add-deltas --delta-order (0 = no deltas; at most 8)              */
+  int32_t delta_window;   /* add-deltas --delta-window (1 .. 999)                             */
+  int32_t left_context;   /* splice-feats --left-context                                      */
+  int32_t right_context;  /* splice-feats --right-context                                     */
+  int32_t device;         /* HIP device; -1 = host-only plan (info and scales only)           */
+} fdlp_post_config;
+/* A batch of concatenated utterances: utterance u is rows row_off[u] .. row_off[u] + utt_len[u] - 1 of both
+ * in_dev [n_rows, dim] and out_dev [n_rows, out_dim] (float32, device).  norm_dev is a device table
+ * [n_norm, 2, dim] of float32 (scale row, offset row: fdlp_cmvn_norm) or NULL for no CMVN; norm_index[u]
+ * picks utterance u's pair (NULL = pair 0), so per-speaker CMVN shares the launch. */
+typedef struct fdlp_post_batch {
+  int32_t n_utt;
+  int32_t norm_mul;            /* 1: multiply by the scale row (--norm-vars or --reverse with it)   */
+  const void* in_dev;
+  int64_t n_rows;
+  const int64_t* row_off;      /* host [n_utt] */
+  const int64_t* utt_len;      /* host [n_utt], every length >= 1 */
+  const void* norm_dev;
+  int32_t n_norm;
+  const int32_t* norm_index;   /* host [n_utt] or NULL */
+  void* out_dev;
+} fdlp_post_batch;
+typedef struct fdlp_post_plan fdlp_post_plan;
+/* FDLP_E_INVALID (the message names the sizes) when one frame per tile does not fit the 160 KB LDS. */
+int fdlp_post_plan_create(const fdlp_post_config* cfg, fdlp_post_plan** out);
+int fdlp_post_plan_destroy(fdlp_post_plan* plan);
+/* out_dim = (L + R + 1) * D * (order + 1) with D = truncate or dim; frames per workgroup tile; LDS bytes of a
+ * workgroup.  Any pointer may be NULL. */
+int fdlp_post_plan_info(const fdlp_post_plan* plan, int32_t* out_dim, int32_t* tile, int32_t* lds_bytes);
+/* The delta filters: lens[order + 1] (2 i window + 1) and the tables concatenated in `scales`
+ * (sum of lens floats).  scales[0] = [1]; scales[i] is scales[i-1] convolved with j = -window .. window over
+ * sum j^2, kept as exact integer numerators over (sum j^2)^i and rounded to float32 once.  Either may be NULL. */
+int fdlp_post_plan_scales(const fdlp_post_plan* plan, int32_t* lens, float* scales);
+int fdlp_post_compute(fdlp_post_plan* plan, const fdlp_post_batch* batch, void* stream);
+/* ApplyCmvn / ApplyCmvnReverse as two float32 vectors: out[0 .. dim) = scale, out[dim .. 2 dim) = offset, from the
+ * [2, dim + 1] double stats compute-cmvn-stats writes (count = stats[dim]; count < 1 is FDLP_E_INVALID).
+ * mean = s0/count; norm_vars: var = s1/count - mean^2 floored at 1e-20 (a warning on stderr), scale = 1/sqrt(var),
+ * offset = -mean * scale (a non-finite scale is FDLP_E_INVALID); reverse: scale = sqrt(var) (or 1), offset = mean;
+ * skip_dims columns get scale 1, offset 0; norm_vars without norm_means is FDLP_E_INVALID; neither gives the
+ * identity.  Host only. */
+int fdlp_cmvn_norm(const double* stats, int32_t dim, int32_t norm_means, int32_t norm_vars, int32_t reverse,
+                   const int32_t* skip_dims, int32_t n_skip, float* out);
+
 /* ---- augmentation: addReverb (features.py:110-115) -------------------------------------- */
 /* --add_reverb small_room|medium_room|large_room (computeFDLPSpectrogram.py:75-91, :168-170): after the
  * optional diff / noise preprocessing, every utterance is convolved with the RIR (channel 1 of

@@ -91,6 +91,20 @@ class FdlpMfccConfigC(ctypes.Structure):
     ]
 
 
+class FdlpPostConfigC(ctypes.Structure):
+    _fields_ = [
+        ("dim", c_i32), ("truncate", c_i32), ("delta_order", c_i32), ("delta_window", c_i32),
+        ("left_context", c_i32), ("right_context", c_i32), ("device", c_i32),
+    ]
+
+
+class FdlpPostBatchC(ctypes.Structure):
+    _fields_ = [
+        ("n_utt", c_i32), ("norm_mul", c_i32), ("in_dev", c_p), ("n_rows", c_i64), ("row_off", P_i64),
+        ("utt_len", P_i64), ("norm_dev", c_p), ("n_norm", c_i32), ("norm_index", P_i32), ("out_dev", c_p),
+    ]
+
+
 class FdlpReverbBatchC(ctypes.Structure):
     _fields_ = [
         ("n_utt", c_i32), ("pcm_kind", c_i32), ("pcm_dev", c_p), ("pcm_off", P_i64), ("utt_len", P_i64),
@@ -185,6 +199,12 @@ SIGNATURES = {
     "fdlp_mfcc_geometry": (c_i32, [c_p, c_i64, P_i32, P_i32]),
     "fdlp_mfcc_compute": (c_i32, [c_p, ctypes.POINTER(FdlpBatchC), c_p]),
     "fdlp_mfcc_plan_tables": (c_i32, [c_p, P_i32, P_dbl, P_dbl, P_dbl]),
+    "fdlp_post_plan_create": (c_i32, [ctypes.POINTER(FdlpPostConfigC), ctypes.POINTER(c_p)]),
+    "fdlp_post_plan_destroy": (c_i32, [c_p]),
+    "fdlp_post_plan_info": (c_i32, [c_p, P_i32, P_i32, P_i32]),
+    "fdlp_post_plan_scales": (c_i32, [c_p, P_i32, ctypes.POINTER(ctypes.c_float)]),
+    "fdlp_post_compute": (c_i32, [c_p, ctypes.POINTER(FdlpPostBatchC), c_p]),
+    "fdlp_cmvn_norm": (c_i32, [P_dbl, c_i32, c_i32, c_i32, c_i32, P_i32, c_i32, ctypes.POINTER(ctypes.c_float)]),
     "fdlp_noise_params_f64": (c_i32, [P_dbl, c_i64, P_i16, c_i64, c_dbl, c_dbl, P_i64, P_dbl]),
     "fdlp_mat_reader_open": (c_i32, [ctypes.c_char_p, ctypes.POINTER(c_p)]),
     "fdlp_mat_reader_next": (c_i32, [c_p, ctypes.POINTER(ctypes.c_char_p), P_i32, P_i32,

@@ -263,6 +263,50 @@ int fdlp_noise_params_f64(const double* sig, int64_t T, const int16_t* noise, in
   return FDLP_OK;
 }
 
+// ApplyCmvn / ApplyCmvnReverse (transform/cmvn.cc) reduced to the two float32 vectors the device applies:
+// y = fl32(fl32(x * scale) + offset).  All arithmetic in double, rounded once.
+int fdlp_cmvn_norm(const double* stats, int32_t dim, int32_t norm_means, int32_t norm_vars, int32_t reverse,
+                   const int32_t* skip_dims, int32_t n_skip, float* out) {
+  if (!stats || !out || dim < 1 || n_skip < 0 || (n_skip > 0 && !skip_dims))
+    return fdlp::fail(FDLP_E_INVALID, "fdlp_cmvn_norm: bad args");
+  if (norm_vars && !norm_means)
+    return fdlp::fail(FDLP_E_INVALID, "You cannot normalize the variance but not the mean.");
+  for (int32_t i = 0; i < n_skip; ++i)
+    if (skip_dims[i] < 0 || skip_dims[i] >= dim)
+      return fdlp::fail(FDLP_E_INVALID, "--skip-dims: dimension " + std::to_string(skip_dims[i]) +
+                                            " is out of range for features of dimension " + std::to_string(dim));
+  const double count = stats[dim];
+  if (!(count >= 1.0))
+    return fdlp::fail(FDLP_E_INVALID, "Insufficient stats for cepstral mean and variance normalization: count = " +
+                                          std::to_string(count));
+  const double* s0 = stats;
+  const double* s1 = stats + (dim + 1);
+  for (int32_t d = 0; d < dim; ++d) {
+    double scale = 1.0, offset = 0.0;
+    if (norm_means) {
+      const double mean = s0[d] / count;
+      if (norm_vars) {
+        double var = s1[d] / count - mean * mean;
+        if (var < 1.0e-20) {
+          fprintf(stderr, "WARNING (apply-cmvn) Flooring cepstral variance from %g to 1e-20\n", var);
+          var = 1.0e-20;
+        }
+        scale = reverse ? sqrt(var) : 1.0 / sqrt(var);
+        if (!(scale == scale) || !(fabs(scale) <= 1.79769313486231570e308) || 1.0 / scale == 0.0)
+          return fdlp::fail(FDLP_E_INVALID, "NaN or infinity in cepstral mean/variance computation");
+      }
+      offset = reverse ? mean : -(mean * scale);
+    }
+    out[d] = (float)scale;
+    out[dim + d] = (float)offset;
+  }
+  for (int32_t i = 0; i < n_skip; ++i) {
+    out[skip_dims[i]] = 1.0f;
+    out[dim + skip_dims[i]] = 0.0f;
+  }
+  return FDLP_OK;
+}
+
 // Compact ark codes -> the float32 ark values (fdlp_batch.out_q_dev, fdlp_device.h q_code): the device
 // stores (float)(k / 10^d) in out_dev; here the same two IEEE operations on the same k, so the floats
 // are bitwise the ones the device would have written.  -32768 is -0.0.  The 65536 values of a decimals

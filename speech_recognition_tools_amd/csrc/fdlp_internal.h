@@ -222,6 +222,28 @@ hipError_t launch_mfcc(const MfccConsts& c, const MfccFrame* frames, int nframes
 size_t mfcc_lds_bytes(int rt, int Kpad, int nbpad, int nfilters);
 int mfcc_row_tiles(int Kpad, int nbpad, int nfilters);  // 16-frame row tiles per workgroup (2, 1; 0 = too large)
 
+// Post-processing chain (apply-cmvn | add-deltas | splice-feats, fdlp_post.hip): one tile of consecutive
+// frames of one utterance and the plan constants.
+constexpr int kPostMaxOrder = 8;
+struct PostTile {
+  int64_t row0;            // batch row of the utterance's frame 0 (input and output rows coincide)
+  int32_t T, t0, norm, pad_;  // utterance frames, first frame of the tile, index into the norm table
+};
+struct PostConsts {
+  int Din, D, order, window, L, R, tf;  // input columns, columns kept (--truncate), ..., frames per tile
+  int Dp, Dout;                         // D (order + 1), (L + R + 1) Dp
+  int a_floats;                         // floats of the LDS input tile (0 without deltas)
+  int kstep, rstep;                     // 1024 = rstep Dout + kstep (the store loop's stride)
+  int vec4;                             // 16-byte loads: Din, D multiples of 4 and aligned pointers
+  int soff[kPostMaxOrder + 1];          // scales[i] starts at scales + soff[i], 2 i window + 1 taps
+  const float* scales;
+};
+hipError_t launch_post(const PostConsts& c, const PostTile* tiles, int ntiles, const float* x, int64_t n_rows,
+                       const float* norm, int norm_mul, float* out, hipStream_t s);
+size_t post_lds_bytes(int tf, int D, int order, int window, int L, int R);
+int post_pick_tile(int D, int order, int window, int L, int R);  // frames per tile, 0 = does not fit the LDS
+hipError_t checks_post(unsigned int* v, bool reset);
+
 // One utterance of a reverb batch (fdlp_reverb): samples at pcm[off, off+T), y at [yoff, yoff+T+R-1).
 struct RevUtt {
   int64_t off, T, yoff, noff;  // noff < 0: no noise mixing

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -1244,7 +1245,7 @@ int fdlp_set_debug(fdlp_plan* p, int32_t keep_intermediates) {
 int fdlp_device_checks(int32_t* enabled, uint32_t* violations, uint32_t* last_line, int32_t reset) {
   unsigned int tot = 0, line = 0;
   hipError_t (*const fns[])(unsigned int*, bool) = {fdlp::checks_dct, fdlp::checks_autocorr, fdlp::checks_lpc,
-                                                    fdlp::checks_misc};
+                                                    fdlp::checks_misc, fdlp::checks_post};
   HIP_TRY(hipDeviceSynchronize());
   for (auto fn : fns) {
     unsigned int v[2] = {0u, 0u};
@@ -1707,6 +1708,211 @@ int fdlp_mfcc_compute(fdlp_mfcc_plan* p, const fdlp_batch* b, void* stream) {
   p->staging_pending = true;
   HIP_TRY(fdlp::launch_mfcc(p->mc, p->d_frames, nf, b->pcm_dev, b->pcm_kind, b->noise_dev, p->d_cep, b->out_dev,
                             b->out_f64_dev, b->ark_decimals, s));
+  return FDLP_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Post-processing plan (apply-cmvn | add-deltas | splice-feats, fdlp_post.hip)
+// ---------------------------------------------------------------------------------------------
+struct fdlp_post_plan {
+  fdlp_post_config cfg{};
+  int D = 0, Dp = 0, Dout = 0, tf = 0;
+  size_t lds = 0;
+  std::vector<int32_t> lens;
+  std::vector<float> scales;  // concatenated tables
+  fdlp::PostConsts pc{};
+  float* d_scales = nullptr;
+  fdlp::PostTile* d_tiles = nullptr;
+  fdlp::PostTile* h_tiles = nullptr;  // pinned staging
+  size_t tile_cap = 0;
+  hipEvent_t staging_done = nullptr;
+  bool staging_pending = false;
+};
+
+static int free_post_plan(fdlp_post_plan* p) {
+  if (!p) return FDLP_OK;
+  if (p->d_scales) (void)hipFree(p->d_scales);
+  if (p->d_tiles) (void)hipFree(p->d_tiles);
+  if (p->h_tiles) (void)hipHostFree(p->h_tiles);
+  if (p->staging_done) (void)hipEventDestroy(p->staging_done);
+  delete p;
+  return FDLP_OK;
+}
+
+// DeltaFeatures' scale tables.  scales[i] = scales[i-1] convolved with j = -window .. window, over sum j^2: the
+// numerators are integers (exact in double), the denominator is (sum j^2)^i, one rounding to float32.
+static void post_scale_tables(int order, int window, std::vector<int32_t>& lens, std::vector<float>& flat) {
+  std::vector<double> prev{1.0};
+  double denom = 1.0, norm = 0.0;
+  for (int j = -window; j <= window; ++j) norm += (double)j * j;
+  lens.assign(1, 1);
+  flat.assign(1, 1.0f);
+  for (int i = 1; i <= order; ++i) {
+    const int po = ((int)prev.size() - 1) / 2, co = po + window;
+    std::vector<double> cur(prev.size() + 2 * (size_t)window, 0.0);
+    for (int j = -window; j <= window; ++j)
+      for (int k = -po; k <= po; ++k) cur[(size_t)(j + k + co)] += (double)j * prev[(size_t)(k + po)];
+    denom *= norm;
+    lens.push_back((int32_t)cur.size());
+    for (double v : cur) flat.push_back((float)(v / denom));
+    prev.swap(cur);
+  }
+}
+
+int fdlp_post_plan_create(const fdlp_post_config* cfg, fdlp_post_plan** out) {
+  if (!cfg || !out) return fail(FDLP_E_INVALID, "fdlp_post_plan_create: null argument");
+  *out = nullptr;
+  const fdlp_post_config& c = *cfg;
+  if (c.dim < 1 || c.truncate < 0 || c.left_context < 0 || c.right_context < 0 || c.delta_order < 0)
+    return fail(FDLP_E_INVALID, "invalid post configuration (dim >= 1, truncate, contexts and delta order >= 0)");
+  if (c.truncate > c.dim)
+    return fail(FDLP_E_INVALID, "Cannot truncate features as dimension " + std::to_string(c.dim) +
+                                    " is smaller than truncation dimension " + std::to_string(c.truncate));
+  if (c.delta_order > fdlp::kPostMaxOrder) return fail(FDLP_E_INVALID, "delta order above 8 is not supported");
+  if (c.delta_order > 0 && (c.delta_window < 1 || c.delta_window >= 1000))
+    return fail(FDLP_E_INVALID, "delta window must be in 1 .. 999");
+  if (c.left_context > 100000 || c.right_context > 100000) return fail(FDLP_E_INVALID, "context too large");
+  auto* p = new (std::nothrow) fdlp_post_plan;
+  if (!p) return fail(FDLP_E_NOMEM, "out of memory");
+  p->cfg = c;
+  const int window = c.delta_order > 0 ? c.delta_window : 0;
+  p->cfg.delta_window = window;
+  p->D = c.truncate > 0 ? c.truncate : c.dim;
+  const int64_t Dp = (int64_t)p->D * (c.delta_order + 1);
+  const int64_t Dout = Dp * (c.left_context + c.right_context + 1);
+  p->tf = Dout < (1 << 24) ? fdlp::post_pick_tile(p->D, c.delta_order, window, c.left_context, c.right_context) : 0;
+  if (p->tf == 0) {
+    const double need = Dout < (1 << 24)
+        ? (double)fdlp::post_lds_bytes(1, p->D, c.delta_order, window, c.left_context, c.right_context) : 4.0 * Dout;
+    free_post_plan(p);
+    char msg[320];
+    snprintf(msg, sizeof msg, "post plan does not fit the 160 KB LDS at one frame per tile: dim %d, delta order %d "
+             "window %d, context -%d..+%d give %lld output columns and need %.0f bytes",
+             (int)(c.truncate > 0 ? c.truncate : c.dim), (int)c.delta_order, window, (int)c.left_context,
+             (int)c.right_context, (long long)Dout, need);
+    return fail(FDLP_E_INVALID, msg);
+  }
+  p->Dp = (int)Dp;
+  p->Dout = (int)Dout;
+  p->lds = fdlp::post_lds_bytes(p->tf, p->D, c.delta_order, window, c.left_context, c.right_context);
+  post_scale_tables(c.delta_order, window, p->lens, p->scales);
+  fdlp::PostConsts& k = p->pc;
+  k.Din = c.dim; k.D = p->D; k.order = c.delta_order; k.window = window; k.L = c.left_context; k.R = c.right_context;
+  k.tf = p->tf; k.Dp = p->Dp; k.Dout = p->Dout;
+  k.a_floats = (int)((p->lds / sizeof(float)) - ((size_t)p->tf + k.L + k.R) * p->Dp);
+  k.kstep = 1024 % p->Dout; k.rstep = 1024 / p->Dout;
+  int off = 0;
+  for (int i = 0; i <= fdlp::kPostMaxOrder; ++i) {
+    k.soff[i] = off;
+    if (i <= c.delta_order) off += p->lens[(size_t)i];
+  }
+  if (c.device < 0) {
+    *out = p;
+    return FDLP_OK;
+  }
+  int rc, ndev = 0;
+#define POST_FAIL(code, msg) do { rc = fail(code, msg); free_post_plan(p); return rc; } while (0)
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) POST_FAIL(FDLP_E_HIP, "no HIP device visible");
+  if (c.device >= ndev) POST_FAIL(FDLP_E_INVALID, "device index out of range");
+  DeviceGuard dg(c.device);
+  if (dg.status() != hipSuccess) POST_FAIL(FDLP_E_HIP, "hipSetDevice failed");
+  rc = upload(&p->d_scales, p->scales.data(), p->scales.size());
+  if (rc != FDLP_OK) {
+    std::string m_ = fdlp::last_error_slot();
+    free_post_plan(p);
+    fdlp::last_error_slot() = m_;
+    return rc;
+  }
+  if (hipEventCreateWithFlags(&p->staging_done, hipEventDisableTiming) != hipSuccess)
+    POST_FAIL(FDLP_E_NOMEM, "post plan event creation failed");
+#undef POST_FAIL
+  k.scales = p->d_scales;
+  *out = p;
+  return FDLP_OK;
+}
+
+int fdlp_post_plan_destroy(fdlp_post_plan* p) {
+  if (p && p->cfg.device >= 0) {
+    DeviceGuard dg(p->cfg.device);
+    if (p->staging_pending) (void)hipEventSynchronize(p->staging_done);
+    return free_post_plan(p);
+  }
+  return free_post_plan(p);
+}
+
+int fdlp_post_plan_info(const fdlp_post_plan* p, int32_t* out_dim, int32_t* tile, int32_t* lds_bytes) {
+  if (!p) return fail(FDLP_E_INVALID, "fdlp_post_plan_info: null plan");
+  if (out_dim) *out_dim = p->Dout;
+  if (tile) *tile = p->tf;
+  if (lds_bytes) *lds_bytes = (int32_t)p->lds;
+  return FDLP_OK;
+}
+
+int fdlp_post_plan_scales(const fdlp_post_plan* p, int32_t* lens, float* scales) {
+  if (!p) return fail(FDLP_E_INVALID, "fdlp_post_plan_scales: null plan");
+  if (lens) memcpy(lens, p->lens.data(), sizeof(int32_t) * p->lens.size());
+  if (scales) memcpy(scales, p->scales.data(), sizeof(float) * p->scales.size());
+  return FDLP_OK;
+}
+
+int fdlp_post_compute(fdlp_post_plan* p, const fdlp_post_batch* b, void* stream) {
+  if (!p || !b || p->cfg.device < 0) return fail(FDLP_E_INVALID, "fdlp_post_compute: bad args or host-only plan");
+  if (b->n_utt < 0 || b->n_rows < 0 || (b->n_utt > 0 && (!b->in_dev || !b->out_dev || !b->row_off || !b->utt_len)))
+    return fail(FDLP_E_INVALID, "fdlp_post_compute: bad batch");
+  if (b->norm_dev && b->n_norm < 1) return fail(FDLP_E_INVALID, "fdlp_post_compute: empty norm table");
+  if (((uintptr_t)b->in_dev | (uintptr_t)b->out_dev | (uintptr_t)b->norm_dev) & 3u)
+    return fail(FDLP_E_INVALID, "fdlp_post_compute: pointers must be 4-byte aligned");
+  size_t nt = 0;
+  for (int u = 0; u < b->n_utt; ++u) {
+    const int64_t T = b->utt_len[u], r0 = b->row_off[u];
+    if (T < 1 || T > INT32_MAX - 2 * 1100000 || r0 < 0 || r0 > b->n_rows - T)
+      return fail(FDLP_E_INVALID, "utterance " + std::to_string(u) + " is empty or outside the batch's rows");
+    if (b->norm_dev && b->norm_index && (b->norm_index[u] < 0 || b->norm_index[u] >= b->n_norm))
+      return fail(FDLP_E_INVALID, "norm_index out of range for utterance " + std::to_string(u));
+    nt += (size_t)((T + p->tf - 1) / p->tf);
+  }
+  if (nt == 0) return FDLP_OK;
+  if (nt > (size_t)INT32_MAX) return fail(FDLP_E_CAPACITY, "too many tiles in one batch");
+  DeviceGuard dg(p->cfg.device);
+  HIP_TRY(dg.status());
+  hipStream_t s = (hipStream_t)stream;
+  if (p->staging_pending) {
+    HIP_TRY(hipEventSynchronize(p->staging_done));
+    p->staging_pending = false;
+  }
+  if (nt > p->tile_cap) {
+    // the previous batch's kernel may still read d_tiles
+    HIP_TRY(hipDeviceSynchronize());
+    if (p->d_tiles) (void)hipFree(p->d_tiles);
+    if (p->h_tiles) (void)hipHostFree(p->h_tiles);
+    p->d_tiles = nullptr;
+    p->h_tiles = nullptr;
+    p->tile_cap = 0;
+    const size_t cap = std::max<size_t>(nt + nt / 2, 1024);
+    if (hipMalloc((void**)&p->d_tiles, sizeof(fdlp::PostTile) * cap) != hipSuccess ||
+        hipHostMalloc((void**)&p->h_tiles, sizeof(fdlp::PostTile) * cap, hipHostMallocDefault) != hipSuccess)
+      return fail(FDLP_E_NOMEM, "post plan tile table allocation failed");
+    p->tile_cap = cap;
+  }
+  size_t k = 0;
+  for (int u = 0; u < b->n_utt; ++u) {
+    const int64_t T = b->utt_len[u];
+    for (int64_t t0 = 0; t0 < T; t0 += p->tf) {
+      fdlp::PostTile& tl = p->h_tiles[k++];
+      tl.row0 = b->row_off[u];
+      tl.T = (int32_t)T;
+      tl.t0 = (int32_t)t0;
+      tl.norm = b->norm_dev && b->norm_index ? b->norm_index[u] : 0;
+      tl.pad_ = 0;
+    }
+  }
+  fdlp::PostConsts pc = p->pc;
+  pc.vec4 = pc.Din % 4 == 0 && pc.D % 4 == 0 && (((uintptr_t)b->in_dev | (uintptr_t)b->norm_dev) & 15u) == 0;
+  HIP_TRY(hipMemcpyAsync(p->d_tiles, p->h_tiles, sizeof(fdlp::PostTile) * nt, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipEventRecord(p->staging_done, s));
+  p->staging_pending = true;
+  HIP_TRY(fdlp::launch_post(pc, p->d_tiles, (int)nt, (const float*)b->in_dev, b->n_rows, (const float*)b->norm_dev,
+                            b->norm_mul, (float*)b->out_dev, s));
   return FDLP_OK;
 }
 
