@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define FDLP_ABI_VERSION 9
+#define FDLP_ABI_VERSION 10
 
 enum {
   FDLP_OK = 0,
@@ -190,6 +190,22 @@ int fdlp_autocorr_path(const fdlp_plan* plan);
 #define FDLP_LPC_LDS 1
 #define FDLP_LPC_LATTICE8 2
 int fdlp_set_lpc_path(fdlp_plan* plan, int32_t path);
+/* The kernels the LPC stage launches for the plan's current LPC path (ABI 10), answered by the launcher's
+ * own dispatch functions; works on a host-only plan, where fdlp_set_lpc_path only records the path.
+ *   out[0] SL  lanes' coefficients of lpc_env_lattice_kernel<SL, CB, DM>, ceil((p+1)/16); 0 on the LDS path
+ *   out[1] CB  7 the register cepstrum, -1 the sliding-window cepstrum, 0 the LDS cepstrum
+ *   out[2] DM  1 the Durbin inside the lattice kernel, 2 an external Durbin kernel; 0 on the LDS path
+ *   out[3] the Durbin kernel: FDLP_LPC_DURBIN_INREG, FDLP_LPC_DURBIN_4 (durbin4_kernel), 17 / 19 / 21 / 23
+ *          (durbin8_kernel<SL8>), FDLP_LPC_DURBIN_LDS (lpc_env_kernel<TS>) or FDLP_LPC_DURBIN_CPLX
+ *          (complex-modulation plans: cplx_lpc_out_kernel, every other field 0)
+ *   out[4] TS  envelope slots per lane of lpc_env_kernel<TS>; 0 on the lattice path
+ *   out[5] resident blocks of the persistent lattice kernel on the plan's device; 0 on a host-only plan
+ *          and on the LDS path */
+#define FDLP_LPC_DURBIN_INREG 0
+#define FDLP_LPC_DURBIN_4 4
+#define FDLP_LPC_DURBIN_LDS (-1)
+#define FDLP_LPC_DURBIN_CPLX (-2)
+int fdlp_plan_lpc_dispatch(const fdlp_plan* plan, int32_t out[6]);
 /* DCT stage (ABI 5).  FDLP_DCT_AUTO (plan default): for the recipes' frame length N = 24000 one kernel per
  * frame (dct_frame_kernel: the packed 12000-point FFT as three in-register passes with LDS exchanges,
  * D written once); other N, and FDLP_DCT_FOUR_STEP, the two four-step kernels through the Z workspace

@@ -40,7 +40,7 @@ FDLP_MODE_MODSPEC_COMPLEX = 2
 FDLP_WIN_HAMMING = 0
 FDLP_WIN_HANNING = 1
 FDLP_WIN_RECT = 2
-ABI_VERSION = 9
+ABI_VERSION = 10
 FDLP_FN_LOG, FDLP_FN_EXP = 0, 1  # fdlp_device_fn
 STAGE_NAMES = ("frames_dft1", "dft2_dct", "autocorr", "lpc_env", "ola_log")
 
@@ -158,6 +158,7 @@ SIGNATURES = {
     "fdlp_plan_regions": (c_i32, [c_p, c_p, c_p]),
     "fdlp_plan_flat_events": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_i32]),
     "fdlp_set_lpc_path": (c_i32, [c_p, c_i32]),
+    "fdlp_plan_lpc_dispatch": (c_i32, [c_p, P_i32]),
     "fdlp_device_checks": (c_i32, [c_p, c_p, c_p, c_i32]),
     "fdlp_set_dct_path": (c_i32, [c_p, c_i32]),
     "fdlp_dct_path": (c_i32, [c_p]),

@@ -167,6 +167,9 @@ int lpc_env_region(int p, int M);
 // Per-plan launch setup of launch_lpc_env for the current device: sets the kernel's large-LDS
 // attribute and stores the resident block count in c.lpc_blocks.
 hipError_t prepare_lpc_env(DevConsts& c);
+// The kernels launch_lpc_env picks for c, from the launcher's own dispatch functions (no device needed):
+// out = SL, CB, DM, Durbin kernel, TS, lpc_blocks as fdlp_plan_lpc_dispatch documents them.
+void lpc_dispatch_info(const DevConsts& c, int32_t out[6]);
 int autocorr_tiles(int nlags);
 constexpr int kDftMaxSub = 512;  // longest LDS-resident sub-DFT of the four-step DCT
 // Complex modulation spectrum (computeModulationSpectrum.py --complex_modulation): per (frame, band) the

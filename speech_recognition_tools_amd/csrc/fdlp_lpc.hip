@@ -1015,6 +1015,8 @@ __global__ __launch_bounds__(64, lat_waves<CB>()) void lpc_env_lattice_kernel(Lp
     double* la = sh + g * A.region;
     double* cs = la + NAL;
     const int CSN = CB != 0 ? A.Me : M;  // coefficients kept in cs
+    // the item's image: the Durbin's 16 SL positions and a_0 .. a_p inside la, cs behind it inside the region
+    FDLP_CHECK(16 * SL <= NAL && p + 1 <= NAL && A.Me <= CSN && NAL + CSN <= A.region);
     const int H = A.env_nfft >> 1;
     const int TS = (A.env_nfft / 4 + 1 + 15) / 16;
     const int item = ibase + g;
@@ -1093,6 +1095,8 @@ __global__ __launch_bounds__(64, lat_waves<CB>()) void lpc_env_lattice_kernel(Lp
       // reference's range are exact zeros (la is zero from p + 1 to la_len).
       constexpr int W = SL;
       constexpr int R = 4;
+      // the window vectors V_0 .. V_{W-1} of lane l read la[l + 1] .. la[16 W + l]
+      FDLP_CHECK(16 * W + 16 <= A.la_len && A.la_len == NAL);
       double kc[W];  // kc[w]: d (lane l) of block s - 1 - w of the current super-block s; 0 before block 0
 #pragma unroll
       for (int w = 0; w < W; ++w) kc[w] = 0.0;
@@ -1149,6 +1153,8 @@ __global__ __launch_bounds__(64, lat_waves<CB>()) void lpc_env_lattice_kernel(Lp
       const double inv_n = 1.0 / (double)(n > 0 ? n : 1);
       // finished blocks: four independent FMA chains (the trip count is uniform across the wave)
       const int kstart = max(1, b0 - p);
+      // la[n - k] for kstart <= k < b0 stays inside la (zeros past p), cs[k] inside the finished blocks
+      FDLP_CHECK(b0 + 15 - kstart < NAL && b0 <= M && (b0 == 0 || n - (b0 - 1) >= 1));
       double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
       int k = kstart;
       double kd = (double)kstart;
@@ -1222,7 +1228,10 @@ __global__ __launch_bounds__(64, lat_waves<CB>()) void lpc_env_lattice_kernel(Lp
 #pragma unroll
         for (int q = 0; q < kEnvChunk; ++q) {
           const int u = l + 16 * (q0 + q);
-          const double c1 = A.env_cos[decltype(direct)::value ? u : u % A.env_nfft];
+          // (the lanes past u = H / 2 emit nothing: the modulo only keeps their table read inside the table)
+          const int ci = decltype(direct)::value ? u : u % A.env_nfft;
+          FDLP_CHECK(ci >= 0 && ci < A.env_nfft);
+          const double c1 = A.env_cos[ci];
           se[q] = cw[0];
           so[q] = 0.0;
           cprev[q] = 1.0;
@@ -1490,11 +1499,39 @@ static size_t lattice_lds(const DevConsts& c, int CB, int SL) {
   return sizeof(double) * 4 * (size_t)lattice_region(c, CB, SL);
 }
 
+// c.lpc_mode (fdlp_set_lpc_path): 0 = the lattice kernels (durbin8_kernel where p fits it, then the
+// register cepstrum / envelope kernel), 1 = the LDS Durbin kernel (lpc_env_kernel) for every p
+// 2 = the lattice kernels with durbin8_kernel also where durbin4_kernel fits (cross-check)
+static bool lpc_split_for(const DevConsts& c) {
+  return (c.lpc_mode == 0 || c.lpc_mode == 2) && durbin8_fits(c.p);
+}
+// envelope slots per lane of lpc_env_kernel<TS>: u = 0 .. env_nfft/4
+static int lds_env_ts(const DevConsts& c) { return (c.env_nfft / 4 + 1 + 15) / 16; }
+
+// The kernels launch_lpc_env picks for c (fdlp_plan_lpc_dispatch): needs no device, only c.p, c.M,
+// c.env_nfft and c.lpc_mode.  out = SL, CB, DM, Durbin kernel (0 in the lattice kernel, 4 durbin4_kernel,
+// 17..23 durbin8_kernel<SL8>, -1 lpc_env_kernel), TS of lpc_env_kernel, c.lpc_blocks.
+void lpc_dispatch_info(const DevConsts& c0, int32_t out[6]) {
+  DevConsts c = c0;
+  c.lpc_split = lpc_split_for(c);
+  for (int k = 0; k < 6; ++k) out[k] = 0;
+  const hipError_t e = lattice_dispatch(c, [&](auto sl, auto cb, auto dm) -> hipError_t {
+    out[0] = decltype(sl)::value;
+    out[1] = decltype(cb)::value;
+    out[2] = decltype(dm)::value;
+    return hipSuccess;
+  });
+  if (e != hipSuccess) {  // the LDS Durbin kernel
+    out[3] = -1;
+    out[4] = lds_env_ts(c);
+  } else if (out[2] == kDmExt) {
+    out[3] = durbin4_fits(c) ? 4 : durbin8_sl8(c.p);
+  }
+  out[5] = c0.lpc_blocks;
+}
+
 hipError_t prepare_lpc_env(DevConsts& c) {
-  // c.lpc_mode (fdlp_set_lpc_path): 0 = the lattice kernels (durbin8_kernel where p fits it, then the
-  // register cepstrum / envelope kernel), 1 = the LDS Durbin kernel (lpc_env_kernel) for every p
-  // 2 = the lattice kernels with durbin8_kernel also where durbin4_kernel fits (cross-check)
-  c.lpc_split = (c.lpc_mode == 0 || c.lpc_mode == 2) && durbin8_fits(c.p);
+  c.lpc_split = lpc_split_for(c);
   c.lpc_astride = 0;
   c.lpc_blocks = 0;
   int dev = 0, cus = 0;
@@ -1577,7 +1614,7 @@ hipError_t launch_lpc_env(const DevConsts& c, int odd_zero, const double* r, int
     return e;
   }
   const size_t lds = sizeof(double) * (4 * (size_t)A.region);
-  switch ((c.env_nfft / 4 + 1 + 15) / 16) {  // envelope slots: u = 0 .. env_nfft/4
+  switch (lds_env_ts(c)) {
 #define FDLP_TS_CASE(n) case n: return launch_lpc_env_t<n>(A, lds, s);
     FDLP_TS_CASE(1) FDLP_TS_CASE(2) FDLP_TS_CASE(3) FDLP_TS_CASE(4) FDLP_TS_CASE(5) FDLP_TS_CASE(6)
     FDLP_TS_CASE(7) FDLP_TS_CASE(8) FDLP_TS_CASE(9) FDLP_TS_CASE(10) FDLP_TS_CASE(11) FDLP_TS_CASE(12)

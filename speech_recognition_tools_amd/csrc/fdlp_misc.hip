@@ -557,6 +557,8 @@ __global__ __launch_bounds__(64) void cplx_lpc_out_kernel(const double* __restri
   double2* ys = csh;             // nlags
   double2* a = ys + nlags;       // NA: a_0 .. a_p, zeros beyond (alpha = -a past the order is 0)
   double2* cep = a + NA;         // coeff_n
+  // ys is read up to lag p + 1, a up to index max(p, coeff_n - 1), the Durbin update keeps <= 4 values per lane
+  FDLP_CHECK(p + 2 <= nlags && p < NA && coeff_n < NA && p - 1 <= 4 * 64);
   const double2* yi = (const double2*)ycplx + (int64_t)item * nlags;
   for (int l = lane; l < nlags; l += 64) ys[l] = yi[l];
   for (int i = lane; i < NA; i += 64) a[i] = make_double2(i == 0 ? 1.0 : 0.0, 0.0);
@@ -620,6 +622,7 @@ __global__ __launch_bounds__(64) void cplx_lpc_out_kernel(const double* __restri
   const int64_t row = (utts[fd.utt].out_row + fd.k) * (int64_t)B * feat_len + (int64_t)j * feat_len;
   for (int i = lane; i < feat_len; i += 64) {
     const int qq = first + step * i;  // temp2 index
+    FDLP_CHECK(c0 >= 0 && qq >= 0 && c0 + (absval || qq < sel ? qq : qq - sel) < coeff_n);
     double v;
     if (absval) {
       double2 z = cep[c0 + qq];

@@ -782,6 +782,8 @@ int fdlp_plan_create(const fdlp_config* cfg, int device, fdlp_plan** out) {
   const int N = p->N;
 
   p->max_frames = c.max_frames;
+  // what the LPC kernel dispatch reads (fdlp_plan_lpc_dispatch works on a host-only plan too)
+  p->dc.p = p->p; p->dc.nlags = p->nlags; p->dc.M = M; p->dc.Me = p->Me; p->dc.kk = p->kk; p->dc.env_nfft = p->env_nfft;
   if (device < 0) {  // host-only plan: geometry, filterbank, weights and OLA tables, no compute
     phase(0);
     *out = p;
@@ -1186,7 +1188,10 @@ int fdlp_plan_regions(const fdlp_plan* p, int32_t* m1, int32_t* m2) {
 int fdlp_set_lpc_path(fdlp_plan* p, int32_t path) {
   if (!p || (path != FDLP_LPC_AUTO && path != FDLP_LPC_LDS && path != FDLP_LPC_LATTICE8))
     return fail(FDLP_E_INVALID, "fdlp_set_lpc_path: need a plan and FDLP_LPC_AUTO, FDLP_LPC_LDS or FDLP_LPC_LATTICE8");
-  if (p->device < 0) return fail(FDLP_E_INVALID, "fdlp_set_lpc_path: host-only plan");
+  if (p->device < 0) {  // host-only plan: the path is only recorded (fdlp_plan_lpc_dispatch)
+    p->dc.lpc_mode = path;
+    return FDLP_OK;
+  }
   DeviceGuard dg(p->device);
   if (dg.status() != hipSuccess) return fail(FDLP_E_HIP, "hipSetDevice failed");
   p->dc.lpc_mode = path;
@@ -1194,6 +1199,17 @@ int fdlp_set_lpc_path(fdlp_plan* p, int32_t path) {
   if (p->dc.lpc_split && !p->ws.a_pad &&
       hipMalloc((void**)&p->ws.a_pad, sizeof(double) * (size_t)p->max_frames * p->B * p->dc.lpc_astride) != hipSuccess)
     return fail(FDLP_E_NOMEM, "device workspace allocation failed");
+  return FDLP_OK;
+}
+
+int fdlp_plan_lpc_dispatch(const fdlp_plan* p, int32_t out[6]) {
+  if (!p || !out) return fail(FDLP_E_INVALID, "fdlp_plan_lpc_dispatch: need a plan and out[6]");
+  if (p->cplx) {  // cplx_lpc_out_kernel (launch_cplx_modspec), not launch_lpc_env
+    for (int k = 0; k < 6; ++k) out[k] = 0;
+    out[3] = FDLP_LPC_DURBIN_CPLX;
+    return FDLP_OK;
+  }
+  fdlp::lpc_dispatch_info(p->dc, out);
   return FDLP_OK;
 }
 

@@ -185,6 +185,18 @@ class FdlpPlan:
         independent cross-check)."""
         check(lib.fdlp_set_lpc_path(self._h, self.LPC_PATHS[path]))
 
+    def lpc_dispatch(self) -> dict:
+        """The kernels the LPC stage launches for the current LPC path (fdlp_plan_lpc_dispatch; also on a
+        host-only plan): SL, CB (7 register / -1 sliding-window / 0 LDS cepstrum) and DM ('contig' / 'ext',
+        None on the LDS path) of lpc_env_lattice_kernel, ``durbin`` = (kernel, SL8) with kernel one of
+        'inreg', 'durbin4', 'durbin8', 'lds', 'cplx', TS of lpc_env_kernel and the resident lpc_blocks."""
+        v = (_lib.c_i32 * 6)()
+        check(lib.fdlp_plan_lpc_dispatch(self._h, v))
+        sl, cb, dm, dur, ts, blocks = (int(x) for x in v)
+        kind = {0: "inreg", 4: "durbin4", -1: "lds", -2: "cplx"}.get(dur, "durbin8")
+        return dict(SL=sl, CB=cb, DM={0: None, 1: "contig", 2: "ext"}[dm],
+                    durbin=(kind, dur if kind == "durbin8" else 0), TS=ts, lpc_blocks=blocks)
+
     DCT_PATHS = {"auto": 0, "four_step": 1}
 
     def set_dct_path(self, path: str = "auto"):
