@@ -376,6 +376,39 @@ int fdlp_post_plan_info(const fdlp_post_plan* plan, int32_t* out_dim, int32_t* t
  * sum j^2, kept as exact integer numerators over (sum j^2)^i and rounded to float32 once.  Either may be NULL. */
 int fdlp_post_plan_scales(const fdlp_post_plan* plan, int32_t* lens, float* scales);
 int fdlp_post_compute(fdlp_post_plan* plan, const fdlp_post_batch* batch, void* stream);
+
+/* ---- transform-feats: LDA / fMLLR as the last stage of the chain ---------------------------- */
+/* Kaldi's featbin/transform-feats (decode.sh:90 and :116-119, get_Tandem_feats.sh:33-36, the transform-feats
+ * strings of src/nnet/data_prep_*.py), restated from its documented behaviour and fused after the splice in the
+ * same kernel launch (xform_kernel, fdlp_post.hip): the spliced rows stay in LDS and are the A operand of a
+ * float32 MFMA GEMM (v_mfma_f32_16x16x4_f32, exact float32).  With K = fdlp_post_plan_info's out_dim of `post`:
+ *   linear  (affine 0, M [out_dim, K])      out = row M^T
+ *   affine  (affine 1, M [out_dim, K + 1])  out = row M[:, :K]^T + M[:, K]
+ * Every result is one chain acc = fmaf(row[k], M[n][k], acc) from acc = 0 that visits k in the fixed order
+ * "for g = 0, 16, ..: for s = 0 .. 3: for q = 0 .. 3: k = g + 4 q + s" (k >= K skipped), then (affine) one float32
+ * add of M[n][K]: a function of K alone, so a row's result does not depend on the batch, on the tile or on where
+ * its utterance lies.  Kaldi leaves the summation order to its BLAS; the average-logdet log line is not
+ * reproduced.  With every stage of `post` off this is the stand-alone transform-feats. */
+#define FDLP_XFORM_MAX_OUT_DIM 65536
+typedef struct fdlp_xform_config {
+  fdlp_post_config post;  /* the stages before the transform (post.device is the plan's device) */
+  int32_t out_dim;        /* N, rows of the transform matrix: 1 .. FDLP_XFORM_MAX_OUT_DIM          */
+  int32_t affine;         /* 1: the matrices have K + 1 columns, the last one the offset          */
+} fdlp_xform_config;
+typedef struct fdlp_xform_plan fdlp_xform_plan;
+/* FDLP_E_INVALID (the message names the sizes) when out_dim is out of range or one frame per tile, with the
+ * staged matrix chunk beside it, does not fit the 160 KB LDS. */
+int fdlp_xform_plan_create(const fdlp_xform_config* cfg, fdlp_xform_plan** out);
+int fdlp_xform_plan_destroy(fdlp_xform_plan* plan);
+/* in_dim = K, the row width entering the transform; out_dim = N; mat_cols = K + affine; frames per workgroup
+ * tile; LDS bytes of a workgroup.  Works on a host-only plan (post.device = -1).  Any pointer may be NULL. */
+int fdlp_xform_plan_info(const fdlp_xform_plan* plan, int32_t* in_dim, int32_t* out_dim, int32_t* mat_cols,
+                         int32_t* tile, int32_t* lds_bytes);
+/* `batch` as for fdlp_post_compute, except that out_dev is [n_rows, out_dim].  mat_dev: device table
+ * [n_mat, out_dim, mat_cols] of float32; mat_index[u] (host, or NULL = matrix 0) picks utterance u's matrix, so
+ * per-speaker fMLLR shares the launch. */
+int fdlp_xform_compute(fdlp_xform_plan* plan, const fdlp_post_batch* batch, const void* mat_dev, int32_t n_mat,
+                       const int32_t* mat_index, void* stream);
 /* ApplyCmvn / ApplyCmvnReverse as two float32 vectors: out[0 .. dim) = scale, out[dim .. 2 dim) = offset, from the
  * [2, dim + 1] double stats compute-cmvn-stats writes (count = stats[dim]; count < 1 is FDLP_E_INVALID).
  * mean = s0/count; norm_vars: var = s1/count - mean^2 floored at 1e-20 (a warning on stderr), scale = 1/sqrt(var),

@@ -230,8 +230,8 @@ int mfcc_row_tiles(int Kpad, int nbpad, int nfilters);  // 16-frame row tiles pe
 constexpr int kPostMaxOrder = 8;
 struct PostTile {
   int64_t row0;            // batch row of the utterance's frame 0 (input and output rows coincide)
-  int32_t T, t0, norm, pad_;  // utterance frames, first frame of the tile, index into the norm table
-};
+  int32_t T, t0, norm, mat;   // utterance frames, first frame of the tile, index into the norm table, and into
+};                            // the transform table (xform_kernel only)
 struct PostConsts {
   int Din, D, order, window, L, R, tf;  // input columns, columns kept (--truncate), ..., frames per tile
   int Dp, Dout;                         // D (order + 1), (L + R + 1) Dp
@@ -244,7 +244,19 @@ struct PostConsts {
 hipError_t launch_post(const PostConsts& c, const PostTile* tiles, int ntiles, const float* x, int64_t n_rows,
                        const float* norm, int norm_mul, float* out, hipStream_t s);
 size_t post_lds_bytes(int tf, int D, int order, int window, int L, int R);
-int post_pick_tile(int D, int order, int window, int L, int R);  // frames per tile, 0 = does not fit the LDS
+// frames per tile, 0 = does not fit the LDS; extra: bytes needed beside the two tiles
+int post_pick_tile(int D, int order, int window, int L, int R, size_t extra = 0);
+// transform-feats fused after the splice (xform_kernel, fdlp_post.hip): out [n_rows, N] = rows x M[:, :K]^T
+// (+ M[:, K]) with the device table mats [n_mat, N, C], C = K + affine, PostTile::mat picking the matrix.
+struct XformConsts {
+  int N, C, affine, n_mat;
+  int ms_off;  // floats from the start of the LDS to the staged matrix chunk (set by launch_xform)
+};
+hipError_t launch_xform(const PostConsts& c, XformConsts xc, const PostTile* tiles, int ntiles, const float* x,
+                        int64_t n_rows, const float* norm, int norm_mul, const float* mats, float* out,
+                        hipStream_t s);
+size_t xform_ms_bytes(int N);  // LDS bytes of the staged matrix chunk
+size_t xform_lds_bytes(int tf, int D, int order, int window, int L, int R, int N);
 hipError_t checks_post(unsigned int* v, bool reset);
 
 // One utterance of a reverb batch (fdlp_reverb): samples at pcm[off, off+T), y at [yoff, yoff+T+R-1).

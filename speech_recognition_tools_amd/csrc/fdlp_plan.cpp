@@ -1775,8 +1775,8 @@ static void post_scale_tables(int order, int window, std::vector<int32_t>& lens,
   }
 }
 
-int fdlp_post_plan_create(const fdlp_post_config* cfg, fdlp_post_plan** out) {
-  if (!cfg || !out) return fail(FDLP_E_INVALID, "fdlp_post_plan_create: null argument");
+// extra_lds: bytes a workgroup needs beside the two tiles (the transform's matrix chunk, 0 for the plain chain)
+static int post_plan_create(const fdlp_post_config* cfg, fdlp_post_plan** out, size_t extra_lds) {
   *out = nullptr;
   const fdlp_post_config& c = *cfg;
   if (c.dim < 1 || c.truncate < 0 || c.left_context < 0 || c.right_context < 0 || c.delta_order < 0)
@@ -1796,10 +1796,11 @@ int fdlp_post_plan_create(const fdlp_post_config* cfg, fdlp_post_plan** out) {
   p->D = c.truncate > 0 ? c.truncate : c.dim;
   const int64_t Dp = (int64_t)p->D * (c.delta_order + 1);
   const int64_t Dout = Dp * (c.left_context + c.right_context + 1);
-  p->tf = Dout < (1 << 24) ? fdlp::post_pick_tile(p->D, c.delta_order, window, c.left_context, c.right_context) : 0;
+  p->tf = Dout < (1 << 24)
+      ? fdlp::post_pick_tile(p->D, c.delta_order, window, c.left_context, c.right_context, extra_lds) : 0;
   if (p->tf == 0) {
-    const double need = Dout < (1 << 24)
-        ? (double)fdlp::post_lds_bytes(1, p->D, c.delta_order, window, c.left_context, c.right_context) : 4.0 * Dout;
+    const double need = (double)extra_lds + (Dout < (1 << 24)
+        ? (double)fdlp::post_lds_bytes(1, p->D, c.delta_order, window, c.left_context, c.right_context) : 4.0 * Dout);
     free_post_plan(p);
     char msg[320];
     snprintf(msg, sizeof msg, "post plan does not fit the 160 KB LDS at one frame per tile: dim %d, delta order %d "
@@ -1847,6 +1848,11 @@ int fdlp_post_plan_create(const fdlp_post_config* cfg, fdlp_post_plan** out) {
   return FDLP_OK;
 }
 
+int fdlp_post_plan_create(const fdlp_post_config* cfg, fdlp_post_plan** out) {
+  if (!cfg || !out) return fail(FDLP_E_INVALID, "fdlp_post_plan_create: null argument");
+  return post_plan_create(cfg, out, 0);
+}
+
 int fdlp_post_plan_destroy(fdlp_post_plan* p) {
   if (p && p->cfg.device >= 0) {
     DeviceGuard dg(p->cfg.device);
@@ -1871,7 +1877,10 @@ int fdlp_post_plan_scales(const fdlp_post_plan* p, int32_t* lens, float* scales)
   return FDLP_OK;
 }
 
-int fdlp_post_compute(fdlp_post_plan* p, const fdlp_post_batch* b, void* stream) {
+// xc: null for the plain chain; otherwise the transform's constants, with mats [xc->n_mat, N, C] on the device and
+// mat_index[u] (host, or null for matrix 0) carried to the tiles like norm_index
+static int post_compute(fdlp_post_plan* p, const fdlp_post_batch* b, void* stream, const fdlp::XformConsts* xc,
+                        const void* mats, const int32_t* mat_index) {
   if (!p || !b || p->cfg.device < 0) return fail(FDLP_E_INVALID, "fdlp_post_compute: bad args or host-only plan");
   if (b->n_utt < 0 || b->n_rows < 0 || (b->n_utt > 0 && (!b->in_dev || !b->out_dev || !b->row_off || !b->utt_len)))
     return fail(FDLP_E_INVALID, "fdlp_post_compute: bad batch");
@@ -1885,6 +1894,8 @@ int fdlp_post_compute(fdlp_post_plan* p, const fdlp_post_batch* b, void* stream)
       return fail(FDLP_E_INVALID, "utterance " + std::to_string(u) + " is empty or outside the batch's rows");
     if (b->norm_dev && b->norm_index && (b->norm_index[u] < 0 || b->norm_index[u] >= b->n_norm))
       return fail(FDLP_E_INVALID, "norm_index out of range for utterance " + std::to_string(u));
+    if (xc && mat_index && (mat_index[u] < 0 || mat_index[u] >= xc->n_mat))
+      return fail(FDLP_E_INVALID, "mat_index out of range for utterance " + std::to_string(u));
     nt += (size_t)((T + p->tf - 1) / p->tf);
   }
   if (nt == 0) return FDLP_OK;
@@ -1919,7 +1930,7 @@ int fdlp_post_compute(fdlp_post_plan* p, const fdlp_post_batch* b, void* stream)
       tl.T = (int32_t)T;
       tl.t0 = (int32_t)t0;
       tl.norm = b->norm_dev && b->norm_index ? b->norm_index[u] : 0;
-      tl.pad_ = 0;
+      tl.mat = xc && mat_index ? mat_index[u] : 0;
     }
   }
   fdlp::PostConsts pc = p->pc;
@@ -1927,9 +1938,81 @@ int fdlp_post_compute(fdlp_post_plan* p, const fdlp_post_batch* b, void* stream)
   HIP_TRY(hipMemcpyAsync(p->d_tiles, p->h_tiles, sizeof(fdlp::PostTile) * nt, hipMemcpyHostToDevice, s));
   HIP_TRY(hipEventRecord(p->staging_done, s));
   p->staging_pending = true;
-  HIP_TRY(fdlp::launch_post(pc, p->d_tiles, (int)nt, (const float*)b->in_dev, b->n_rows, (const float*)b->norm_dev,
-                            b->norm_mul, (float*)b->out_dev, s));
+  if (xc)
+    HIP_TRY(fdlp::launch_xform(pc, *xc, p->d_tiles, (int)nt, (const float*)b->in_dev, b->n_rows,
+                               (const float*)b->norm_dev, b->norm_mul, (const float*)mats, (float*)b->out_dev, s));
+  else
+    HIP_TRY(fdlp::launch_post(pc, p->d_tiles, (int)nt, (const float*)b->in_dev, b->n_rows,
+                              (const float*)b->norm_dev, b->norm_mul, (float*)b->out_dev, s));
   return FDLP_OK;
+}
+
+int fdlp_post_compute(fdlp_post_plan* p, const fdlp_post_batch* b, void* stream) {
+  return post_compute(p, b, stream, nullptr, nullptr, nullptr);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Transform plan (cmvn | deltas | splice | transform-feats, xform_kernel of fdlp_post.hip): a post plan whose
+// tile leaves room for the staged matrix chunk, and the matrix shape
+// ---------------------------------------------------------------------------------------------
+struct fdlp_xform_plan {
+  fdlp_post_plan* post = nullptr;
+  int N = 0, C = 0, affine = 0;
+  size_t lds = 0;
+};
+
+int fdlp_xform_plan_create(const fdlp_xform_config* cfg, fdlp_xform_plan** out) {
+  if (!cfg || !out) return fail(FDLP_E_INVALID, "fdlp_xform_plan_create: null argument");
+  *out = nullptr;
+  if (cfg->out_dim < 1 || cfg->out_dim > FDLP_XFORM_MAX_OUT_DIM)
+    return fail(FDLP_E_INVALID, "transform rows (out_dim) must be in 1 .. " + std::to_string(FDLP_XFORM_MAX_OUT_DIM) +
+                                    ", got " + std::to_string(cfg->out_dim));
+  auto* x = new (std::nothrow) fdlp_xform_plan;
+  if (!x) return fail(FDLP_E_NOMEM, "out of memory");
+  const int rc = post_plan_create(&cfg->post, &x->post, fdlp::xform_ms_bytes(cfg->out_dim));
+  if (rc != FDLP_OK) {
+    // the post plan's message names the sizes; add the transform's
+    fdlp::last_error_slot() += " (with a transform to " + std::to_string(cfg->out_dim) + " columns, " +
+                               std::to_string(fdlp::xform_ms_bytes(cfg->out_dim)) + " of the bytes)";
+    delete x;
+    return rc;
+  }
+  x->N = cfg->out_dim;
+  x->affine = cfg->affine != 0;
+  x->C = x->post->Dout + x->affine;
+  x->lds = x->post->lds + fdlp::xform_ms_bytes(x->N);
+  *out = x;
+  return FDLP_OK;
+}
+
+int fdlp_xform_plan_destroy(fdlp_xform_plan* x) {
+  if (!x) return FDLP_OK;
+  const int rc = fdlp_post_plan_destroy(x->post);
+  delete x;
+  return rc;
+}
+
+int fdlp_xform_plan_info(const fdlp_xform_plan* x, int32_t* in_dim, int32_t* out_dim, int32_t* mat_cols,
+                         int32_t* tile, int32_t* lds_bytes) {
+  if (!x) return fail(FDLP_E_INVALID, "fdlp_xform_plan_info: null plan");
+  if (in_dim) *in_dim = x->post->Dout;
+  if (out_dim) *out_dim = x->N;
+  if (mat_cols) *mat_cols = x->C;
+  if (tile) *tile = x->post->tf;
+  if (lds_bytes) *lds_bytes = (int32_t)x->lds;
+  return FDLP_OK;
+}
+
+int fdlp_xform_compute(fdlp_xform_plan* x, const fdlp_post_batch* b, const void* mat_dev, int32_t n_mat,
+                       const int32_t* mat_index, void* stream) {
+  if (!x || !b) return fail(FDLP_E_INVALID, "fdlp_xform_compute: null argument");
+  if (x->post->cfg.device < 0) return fail(FDLP_E_INVALID, "fdlp_xform_compute: host-only plan");
+  if (!mat_dev || n_mat < 1 || ((uintptr_t)mat_dev & 3u))
+    return fail(FDLP_E_INVALID, "fdlp_xform_compute: the transform table must be a 4-byte aligned device pointer "
+                                "to at least one matrix");
+  fdlp::XformConsts xc{};
+  xc.N = x->N; xc.C = x->C; xc.affine = x->affine; xc.n_mat = n_mat;
+  return post_compute(x->post, b, stream, &xc, mat_dev, mat_index);
 }
 
 int fdlp_reverb(const fdlp_reverb_batch* b, void* stream) {

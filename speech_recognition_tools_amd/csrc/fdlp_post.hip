@@ -23,6 +23,8 @@ constexpr int kPostThreads = 256;
 constexpr int kPostLdsMax = 160 * 1024;
 constexpr int kPostLdsTarget = 64 * 1024;  // two workgroups per CU: one loads while the other stores
 constexpr int kPostTileMax = 128;
+constexpr int kXfKC = 32;         // columns k of the transform staged in LDS at a time
+constexpr int kXfColBlocks = 4;   // 16-column blocks of the result a wave accumulates at once
 // Stage ablation for benchmarks/post_throughput.py (a variant library built with -DFDLP_POST_SKIP=n, never the
 // default build): bit 0 skips the global loads (frames of zeros), bit 1 the delta filter, bit 2 the stores.
 #ifndef FDLP_POST_SKIP
@@ -39,10 +41,11 @@ size_t post_lds_bytes(int tf, int D, int order, int window, int L, int R) {
   return sizeof(float) * (post_a_floats(tf, D, order, window, L, R) + ((size_t)tf + L + R) * D * (order + 1));
 }
 
-int post_pick_tile(int D, int order, int window, int L, int R) {
+// extra: LDS bytes the workgroup needs beside the two tiles (the transform's matrix chunk)
+int post_pick_tile(int D, int order, int window, int L, int R, size_t extra) {
   for (int tf = kPostTileMax; tf >= 1; tf >>= 1)
-    if (post_lds_bytes(tf, D, order, window, L, R) <= (size_t)kPostLdsTarget) return tf;
-  return post_lds_bytes(1, D, order, window, L, R) <= (size_t)kPostLdsMax ? 1 : 0;
+    if (post_lds_bytes(tf, D, order, window, L, R) + extra <= (size_t)kPostLdsTarget) return tf;
+  return post_lds_bytes(1, D, order, window, L, R) + extra <= (size_t)kPostLdsMax ? 1 : 0;
 }
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
@@ -78,11 +81,172 @@ struct DivStep {
   }
 };
 
-template <int MODE>
-__global__ __launch_bounds__(kPostThreads) void post_kernel(PostConsts c, const PostTile* __restrict__ tiles,
-                                                            const float* __restrict__ x, int64_t n_rows,
-                                                            const float* __restrict__ norm, int norm_mul,
-                                                            float* __restrict__ out) {
+// -----------------------------------------------------------------------------------------------------------
+// transform-feats as the last stage: out[r][n] = sum_k A[r][k] M[n][k] (+ M[n][K]) with the tile's spliced rows
+// A[r][k] = B[r D' + k] (an implicit im2col: nothing is copied) on v_mfma_f32_16x16x4_f32, which is exact float32:
+// each result is one fmaf chain acc = fma(A[r][k], M[n][k], acc) from acc = 0, one rounding per k, then one float32
+// add of the offset column.  The chain visits k in the order
+//     for g = 0, 16, 32, ..:  for s = 0 .. 3:  for q = 0 .. 3:  k = g + 4 q + s     (k >= K skipped)
+// (MFMA step s of group g takes its four k from the four lane groups q, and a lane group owns four CONSECUTIVE k
+// of a group: with D' a multiple of 4 a lane reads them with one 16-byte LDS load, where k = g + 4 s + q would
+// cost four 4-byte loads whose 16 rows, D' floats apart, collide on the 32 banks of ds_read_b32.)  The order is a
+// function of K alone: not of the tile, of D', of the k-chunks the matrix is staged in, nor of the batch.
+//   * a wave owns the 16-row blocks wave and wave + 4 of the tile and all NCB column blocks of the current group,
+//     so an A operand read from LDS feeds NCB MFMAs and a B operand two;
+//   * the matrix M[n_mat][N][C] is read from global memory in chunks of kXfKC columns k, stored to LDS as
+//     Ms[k][S] (S = 4 mod 8 floats: the k rows 4 q + s of the lane groups q fall into disjoint banks), zero where
+//     k >= K or n >= N, in two buffers: the next chunk's loads are in flight while the current one is
+//     multiplied, and one barrier per chunk separates a buffer's writers from its readers;
+//   * A[r][k >= K] is the next row's data or whatever lies past B, so it is SELECTED to zero, never multiplied
+//     by a zero; rows past tf read row tf - 1 (inside B) and are not stored.
+// -----------------------------------------------------------------------------------------------------------
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+static inline int xform_ncb(int N) { return min((N + 15) / 16, kXfColBlocks); }
+static inline int xform_ms_stride(int ncb) { return ncb * 16 + 4; }
+// two chunks: one is multiplied while the next is written, with one barrier per chunk
+size_t xform_ms_bytes(int N) { return sizeof(float) * 2 * (size_t)kXfKC * xform_ms_stride(xform_ncb(N)); }
+
+// The MFMAs of one staged chunk for a wave's row blocks (TWO: both of them).  mlane: the chunk at row 4 q, column li;
+// k0: the chunk's first k, kq: k0 + 4 q.  FULL: the whole chunk lies below K (no selects), VEC: 16-byte loads of A (D' a multiple of 4).
+template <int NCB, int S, bool TWO, bool FULL, bool VEC>
+__device__ __forceinline__ void xform_chunk(f32x4 (&acc0)[NCB], f32x4 (&acc1)[NCB], const float* __restrict__ B,
+                                            const float* __restrict__ mlane, int a0, int a1, int k0, int kq,
+                                            int K, int blds) {
+  (void)blds;
+  static_assert(FULL || !VEC, "the tail reads element by element");
+#pragma unroll
+  for (int g = 0; g < kXfKC / 16; ++g) {
+    const int kg = kq + 16 * g;  // this lane's k of step s is kg + s
+    if (!FULL && k0 + 16 * g >= K) break;  // the group starts at or past K
+    f32x4 x0, x1 = f32x4{0.f, 0.f, 0.f, 0.f};
+    if constexpr (VEC) {
+      FDLP_CHECK(kg + 3 < K && a0 + kg + 3 < blds && a1 + kg + 3 < blds && ((a0 + kg) & 3) == 0 && ((a1 + kg) & 3) == 0);
+      x0 = *(const f32x4*)(B + a0 + kg);
+      if (TWO) x1 = *(const f32x4*)(B + a1 + kg);
+    } else {
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        const int k = kg + s, kc = FULL ? k : min(k, K - 1);
+        FDLP_CHECK(kc >= 0 && kc < K && a0 + kc < blds && a1 + kc < blds);
+        x0[s] = B[a0 + kc];
+        if (TWO) x1[s] = B[a1 + kc];
+        if (!FULL) {
+          x0[s] = k < K ? x0[s] : 0.f;
+          x1[s] = k < K ? x1[s] : 0.f;
+        }
+      }
+    }
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      if (!FULL && k0 + 16 * g + s >= K) break;  // no lane group has a k < K in this step
+#pragma unroll
+      for (int cb = 0; cb < NCB; ++cb) {
+        const float bv = mlane[(16 * g + s) * S + cb * 16];
+        acc0[cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(x0[s], bv, acc0[cb], 0, 0, 0);
+        if (TWO) acc1[cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(x1[s], bv, acc1[cb], 0, 0, 0);
+      }
+    }
+  }
+}
+
+template <int NCB>
+__device__ __forceinline__ void xform_stage(const PostConsts& c, const XformConsts& xc, const PostTile& tl, int tf,
+                                            int nb, const float* __restrict__ B, float* __restrict__ Ms,
+                                            const float* __restrict__ mats, float* __restrict__ out) {
+  constexpr int S = NCB * 16 + 4;
+  constexpr int NPRE = 2 * NCB;  // NCB 16 kXfKC elements of a chunk over kPostThreads threads
+  static_assert(kXfKC == 32 && kPostThreads == 256, "the chunk's element map below");
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // in an SGPR: the branches on it are scalar
+  const int K = c.Dout, Dp = c.Dp, N = xc.N, C = xc.C;
+  const int blds = nb * Dp;
+  const float* __restrict__ Mg = mats + (size_t)tl.mat * N * C;
+  float* o = out + (tl.row0 + tl.t0) * (int64_t)N;
+  const int li = lane & 15, lq = lane >> 4;
+  const int nrb = (tf + 15) >> 4;
+  const bool act0 = wave < nrb, act1 = wave + 4 < nrb;
+  const int a0 = min(wave * 16 + li, tf - 1) * Dp, a1 = min((wave + 4) * 16 + li, tf - 1) * Dp;
+  // chunk element i of this thread: column block i / 2, k row 4 wave + lq + 16 (i % 2), column li of the block
+  const int ekq = 4 * wave + lq;
+  const bool vec = (Dp & 3) == 0;  // B is 16-byte aligned (post_a_floats), so every row of it is
+  FDLP_CHECK(xc.ms_off >= c.a_floats + (c.tf + c.L + c.R) * Dp && tl.mat >= 0 && tl.mat < xc.n_mat);
+
+  for (int n0 = 0; n0 < N; n0 += NCB * 16) {
+    f32x4 acc0[NCB], acc1[NCB];
+#pragma unroll
+    for (int cb = 0; cb < NCB; ++cb) acc0[cb] = acc1[cb] = f32x4{0.f, 0.f, 0.f, 0.f};
+    float pre[NPRE];
+    auto fetch = [&](int k0) {
+#pragma unroll
+      for (int i = 0; i < NPRE; ++i) {
+        const int n = n0 + (i >> 1) * 16 + li, k = k0 + ekq + 16 * (i & 1);
+        float v = 0.f;
+        if (n < N && k < K) {
+          FDLP_CHECK((int64_t)n * C + k < (int64_t)N * C);
+          v = Mg[(size_t)n * C + k];
+        }
+        pre[i] = v;
+      }
+    };
+    fetch(0);
+    __syncthreads();  // the previous group's last chunk has been read
+    int buf = 0;
+    for (int k0 = 0; k0 < K; k0 += kXfKC, buf ^= 1) {
+      float* Mc = Ms + buf * (kXfKC * S);  // read two barriers ago
+#pragma unroll
+      for (int i = 0; i < NPRE; ++i) {
+        const int at = (ekq + 16 * (i & 1)) * S + (i >> 1) * 16 + li;
+        FDLP_CHECK(at >= 0 && at < kXfKC * S);
+        Mc[at] = pre[i];
+      }
+      __syncthreads();
+      if (k0 + kXfKC < K) fetch(k0 + kXfKC);
+      if (!act0) continue;
+      const float* mlane = Mc + 4 * lq * S + li;
+      const int kq = k0 + 4 * lq;
+      if (k0 + kXfKC <= K) {
+        if (vec) {
+          if (act1) xform_chunk<NCB, S, true, true, true>(acc0, acc1, B, mlane, a0, a1, k0, kq, K, blds);
+          else xform_chunk<NCB, S, false, true, true>(acc0, acc1, B, mlane, a0, a1, k0, kq, K, blds);
+        } else {
+          if (act1) xform_chunk<NCB, S, true, true, false>(acc0, acc1, B, mlane, a0, a1, k0, kq, K, blds);
+          else xform_chunk<NCB, S, false, true, false>(acc0, acc1, B, mlane, a0, a1, k0, kq, K, blds);
+        }
+      } else {
+        if (act1) xform_chunk<NCB, S, true, false, false>(acc0, acc1, B, mlane, a0, a1, k0, kq, K, blds);
+        else xform_chunk<NCB, S, false, false, false>(acc0, acc1, B, mlane, a0, a1, k0, kq, K, blds);
+      }
+    }
+    // results: lane holds column li of rows 4 lq .. 4 lq + 3 of each 16 x 16 block
+#pragma unroll
+    for (int cb = 0; cb < NCB; ++cb) {
+      const int n = n0 + cb * 16 + li;
+      if (n >= N) continue;
+      const float off = xc.affine ? Mg[(size_t)n * C + K] : 0.f;
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        if (!(h ? act1 : act0)) continue;
+        const f32x4 a = h ? acc1[cb] : acc0[cb];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int r = (wave + 4 * h) * 16 + 4 * lq + q;
+          if (r >= tf) continue;
+          FDLP_CHECK(r >= 0 && tl.t0 + r < tl.T && n < N);
+          o[(int64_t)r * N + n] = xc.affine ? __fadd_rn(a[q], off) : a[q];
+        }
+      }
+    }
+  }
+}
+
+// NCB = 0: the rows are streamed out (post_kernel); NCB = 1 .. kXfColBlocks: they are multiplied by the transform
+// instead, NCB 16-column blocks of the result at a time (xform_kernel, xform_stage above).
+template <int MODE, int NCB>
+__device__ __forceinline__ void post_body(const PostConsts& c, const PostTile* __restrict__ tiles,
+                                          const float* __restrict__ x, int64_t n_rows,
+                                          const float* __restrict__ norm, int norm_mul, float* __restrict__ out,
+                                          const XformConsts& xc, const float* __restrict__ mats) {
   extern __shared__ float4 post_sh4[];
   float* sh = (float*)post_sh4;
   const PostTile tl = tiles[blockIdx.x];
@@ -212,6 +376,10 @@ __global__ __launch_bounds__(kPostThreads) void post_kernel(PostConsts c, const 
   }
   __syncthreads();
 
+  if constexpr (NCB > 0) {
+    xform_stage<NCB>(c, xc, tl, tf, nb, B, sh + xc.ms_off, mats, out);
+    return;
+  }
   // 3. the tile's output range [(row0 + t0) Dout, (row0 + t0 + tf) Dout): element g is row r = g / Dout,
   //    column k = g % Dout, and lives at B[r D' + k]
   if (FDLP_POST_SKIP & 4) return;
@@ -254,6 +422,24 @@ __global__ __launch_bounds__(kPostThreads) void post_kernel(PostConsts c, const 
   }
 }
 
+template <int MODE>
+__global__ __launch_bounds__(kPostThreads) void post_kernel(PostConsts c, const PostTile* __restrict__ tiles,
+                                                            const float* __restrict__ x, int64_t n_rows,
+                                                            const float* __restrict__ norm, int norm_mul,
+                                                            float* __restrict__ out) {
+  post_body<MODE, 0>(c, tiles, x, n_rows, norm, norm_mul, out, XformConsts{}, nullptr);
+}
+
+template <int MODE, int NCB>
+__global__ __launch_bounds__(kPostThreads) void xform_kernel(PostConsts c, XformConsts xc,
+                                                             const PostTile* __restrict__ tiles,
+                                                             const float* __restrict__ x, int64_t n_rows,
+                                                             const float* __restrict__ norm, int norm_mul,
+                                                             const float* __restrict__ mats,
+                                                             float* __restrict__ out) {
+  post_body<MODE, NCB>(c, tiles, x, n_rows, norm, norm_mul, out, xc, mats);
+}
+
 hipError_t launch_post(const PostConsts& c, const PostTile* tiles, int ntiles, const float* x, int64_t n_rows,
                        const float* norm, int norm_mul, float* out, hipStream_t s) {
   if (ntiles <= 0) return hipSuccess;
@@ -274,6 +460,48 @@ hipError_t launch_post(const PostConsts& c, const PostTile* tiles, int ntiles, c
   }
 #undef FDLP_POST_LAUNCH
   return hipGetLastError();
+}
+
+template <int NCB>
+static hipError_t launch_xform_ncb(const PostConsts& c, const XformConsts& xc, const PostTile* tiles, int ntiles,
+                                   const float* x, int64_t n_rows, const float* norm, int norm_mul,
+                                   const float* mats, float* out, size_t lds, hipStream_t s) {
+  const int mode = c.order == 0 ? -1 : (c.window == kPostSpecWindow && c.order <= kPostSpecMax ? c.order : 0);
+#define FDLP_XFORM_LAUNCH(M)                                                                                  \
+  do {                                                                                                        \
+    if (lds > 65536)                                                                                          \
+      (void)hipFuncSetAttribute((const void*)xform_kernel<M, NCB>, hipFuncAttributeMaxDynamicSharedMemorySize, \
+                                (int)lds);                                                                    \
+    hipLaunchKernelGGL((xform_kernel<M, NCB>), dim3(ntiles), dim3(kPostThreads), lds, s, c, xc, tiles, x,     \
+                       n_rows, norm, norm_mul, mats, out);                                                    \
+  } while (0)
+  switch (mode) {
+    case -1: FDLP_XFORM_LAUNCH(-1); break;
+    case 1: FDLP_XFORM_LAUNCH(1); break;
+    case 2: FDLP_XFORM_LAUNCH(2); break;
+    default: FDLP_XFORM_LAUNCH(0); break;
+  }
+#undef FDLP_XFORM_LAUNCH
+  return hipGetLastError();
+}
+
+size_t xform_lds_bytes(int tf, int D, int order, int window, int L, int R, int N) {
+  return post_lds_bytes(tf, D, order, window, L, R) + xform_ms_bytes(N);
+}
+
+hipError_t launch_xform(const PostConsts& c, XformConsts xc, const PostTile* tiles, int ntiles, const float* x,
+                        int64_t n_rows, const float* norm, int norm_mul, const float* mats, float* out,
+                        hipStream_t s) {
+  if (ntiles <= 0) return hipSuccess;
+  const size_t plds = post_lds_bytes(c.tf, c.D, c.order, c.window, c.L, c.R);
+  const size_t lds = plds + xform_ms_bytes(xc.N);
+  xc.ms_off = (int)(plds / sizeof(float));
+  switch (xform_ncb(xc.N)) {
+    case 1: return launch_xform_ncb<1>(c, xc, tiles, ntiles, x, n_rows, norm, norm_mul, mats, out, lds, s);
+    case 2: return launch_xform_ncb<2>(c, xc, tiles, ntiles, x, n_rows, norm, norm_mul, mats, out, lds, s);
+    case 3: return launch_xform_ncb<3>(c, xc, tiles, ntiles, x, n_rows, norm, norm_mul, mats, out, lds, s);
+    default: return launch_xform_ncb<4>(c, xc, tiles, ntiles, x, n_rows, norm, norm_mul, mats, out, lds, s);
+  }
 }
 
 hipError_t checks_post(unsigned int* v, bool reset) { return fdlp_checks_local(v, reset); }

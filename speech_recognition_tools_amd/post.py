@@ -11,6 +11,13 @@ DeltaFeatures and SpliceFrames; Kaldi itself is not a dependency and parity with
     block i of frame t = sum_j scales[i][j] * y[clamp(t + j, 0, T-1)] in float32, ascending j.
   * splice: row t = rows clamp(t-L) .. clamp(t+R) concatenated (edges replicated).
 All three stages run in post_kernel (csrc/fdlp_post.hip) with no intermediate in HBM.
+
+`transform-feats` (featbin/transform-feats.cc: LDA / MLLT `final.mat`, per-speaker fMLLR) is the optional fourth
+stage, fused after the splice (xform_kernel, same file): with K the row width entering it and M [N, C] float32,
+  * C == K: out = row M^T;  C == K + 1: out = row M[:, :K]^T + M[:, K] (the offset added last, one float32 add);
+  * any other C: the utterance is warned about, counted as an error and not written;
+  * every product is one float32 fmaf chain over k in an order fixed by K alone (Kaldi leaves it to its BLAS);
+  * the average-logdet log line is not reproduced.
 """
 import argparse
 import ctypes
@@ -24,7 +31,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import FdlpPostBatchC, FdlpPostConfigC, check, lib, ptr
+from ._lib import FdlpPostBatchC, FdlpPostConfigC, FdlpXformConfigC, check, lib, ptr
 from .cmvn import MatReader, _bool, read_kaldi_dmatrix
 
 
@@ -60,6 +67,47 @@ def cmvn_norm(stats, norm_means: bool = True, norm_vars: bool = False, reverse: 
                              int(bool(reverse)), ptr(skip, ctypes.c_int32) if skip.size else None, int(skip.size),
                              ptr(out, ctypes.c_float)))
     return out
+
+
+def _make_batch(who, dim, out_dim, feats, lengths, norm, norm_index, norm_vars, offsets, out):
+    """The fdlp_post_batch of a compute call, the output tensor and the host arrays the batch points into."""
+    if feats.dtype != torch.float32 or not feats.is_cuda or feats.dim() != 2 or feats.shape[1] != dim:
+        raise ValueError("%s: need a float32 [rows, %d] device tensor" % (who, dim))
+    feats = feats.contiguous()
+    lens = np.ascontiguousarray(np.asarray(lengths, dtype=np.int64))
+    n = lens.size
+    if offsets is None:
+        offs = np.zeros(n, dtype=np.int64)
+        if n:
+            offs[1:] = np.cumsum(lens)[:-1]
+    else:
+        offs = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
+    rows = feats.shape[0]
+    if out is None:
+        out = torch.empty((rows, out_dim), dtype=torch.float32, device=feats.device)
+    elif (out.dtype != torch.float32 or out.device != feats.device or not out.is_contiguous()
+          or out.dim() != 2 or out.shape[1] != out_dim or out.shape[0] < rows):
+        raise ValueError("%s: out must be a contiguous float32 [>= rows, %d] tensor" % (who, out_dim))
+    b = FdlpPostBatchC()
+    b.n_utt, b.n_rows = n, rows
+    b.in_dev, b.out_dev = feats.data_ptr(), out.data_ptr()
+    b.row_off, b.utt_len = ptr(offs, ctypes.c_int64), ptr(lens, ctypes.c_int64)
+    idx = None
+    if norm is not None:
+        if norm.dtype != torch.float32 or norm.device != feats.device:
+            raise ValueError("%s: norm must be a float32 tensor on the features' device" % who)
+        if norm.dim() == 2:
+            norm = norm.unsqueeze(0)
+        if norm.dim() != 3 or norm.shape[1] != 2 or norm.shape[2] != dim:
+            raise ValueError("%s: norm must be [2, %d] or [n, 2, %d]" % (who, dim, dim))
+        norm = norm.contiguous()
+        b.norm_dev, b.n_norm, b.norm_mul = norm.data_ptr(), norm.shape[0], int(bool(norm_vars))
+        if norm_index is not None:
+            idx = np.ascontiguousarray(np.asarray(norm_index, dtype=np.int32))
+            if idx.size != n:
+                raise ValueError("one norm index per utterance")
+            b.norm_index = ptr(idx, ctypes.c_int32)
+    return b, out, (feats, lens, offs, norm, idx)
 
 
 class PostPlan:
@@ -102,44 +150,68 @@ class PostPlan:
         norm: float32 device tensor [2, dim] or [n, 2, dim] from cmvn_norm, norm_index[u] the pair of utterance u;
         norm_vars=False skips the multiply (the scale row is all ones then).  Returns out [rows, out_dim]; row r
         of the output belongs to input row r."""
-        if feats.dtype != torch.float32 or not feats.is_cuda or feats.dim() != 2 or feats.shape[1] != self.cfg.dim:
-            raise ValueError("PostPlan.compute: need a float32 [rows, %d] device tensor" % self.cfg.dim)
-        feats = feats.contiguous()
-        lens = np.ascontiguousarray(np.asarray(lengths, dtype=np.int64))
-        n = lens.size
-        if offsets is None:
-            offs = np.zeros(n, dtype=np.int64)
-            if n:
-                offs[1:] = np.cumsum(lens)[:-1]
-        else:
-            offs = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
-        rows = feats.shape[0]
-        if out is None:
-            out = torch.empty((rows, self.out_dim), dtype=torch.float32, device=feats.device)
-        elif (out.dtype != torch.float32 or out.device != feats.device or not out.is_contiguous()
-              or out.dim() != 2 or out.shape[1] != self.out_dim or out.shape[0] < rows):
-            raise ValueError("PostPlan.compute: out must be a contiguous float32 [>= rows, %d] tensor" % self.out_dim)
-        b = FdlpPostBatchC()
-        b.n_utt, b.n_rows = n, rows
-        b.in_dev, b.out_dev = feats.data_ptr(), out.data_ptr()
-        b.row_off, b.utt_len = ptr(offs, ctypes.c_int64), ptr(lens, ctypes.c_int64)
-        idx = None
-        if norm is not None:
-            if norm.dtype != torch.float32 or norm.device != feats.device:
-                raise ValueError("PostPlan.compute: norm must be a float32 tensor on the features' device")
-            if norm.dim() == 2:
-                norm = norm.unsqueeze(0)
-            if norm.dim() != 3 or norm.shape[1] != 2 or norm.shape[2] != self.cfg.dim:
-                raise ValueError("PostPlan.compute: norm must be [2, %d] or [n, 2, %d]" % (self.cfg.dim, self.cfg.dim))
-            norm = norm.contiguous()
-            b.norm_dev, b.n_norm, b.norm_mul = norm.data_ptr(), norm.shape[0], int(bool(norm_vars))
-            if norm_index is not None:
-                idx = np.ascontiguousarray(np.asarray(norm_index, dtype=np.int32))
-                if idx.size != n:
-                    raise ValueError("one norm index per utterance")
-                b.norm_index = ptr(idx, ctypes.c_int32)
+        b, out, keep = _make_batch("PostPlan.compute", self.cfg.dim, self.out_dim, feats, lengths, norm, norm_index,
+                                   norm_vars, offsets, out)
         s = stream if stream is not None else torch.cuda.current_stream(feats.device)
         check(lib.fdlp_post_compute(self._h, ctypes.byref(b), ctypes.c_void_p(s.cuda_stream)))
+        return out
+
+
+class XformPlan:
+    """cmvn | deltas | splice | transform-feats in one kernel launch: the stages of `cfg`, then every row times
+    an [out_dim, K (+ 1 when affine)] float32 matrix, K = in_dim being the row width the stages produce.  With
+    every stage of cfg off it is the stand-alone transform-feats.  device=-1 gives a host-only plan (in_dim,
+    out_dim, mat_cols, tile, lds_bytes)."""
+
+    def __init__(self, cfg: PostConfig, out_dim: int, affine: bool = False, device: int = 0):
+        self.cfg = cfg
+        self.device = int(device)
+        c = FdlpXformConfigC()
+        c.post = cfg.to_c(device)
+        c.out_dim, c.affine = int(out_dim), int(bool(affine))
+        h = ctypes.c_void_p()
+        check(lib.fdlp_xform_plan_create(ctypes.byref(c), ctypes.byref(h)))
+        self._h = h
+        v = [_lib.c_i32() for _ in range(5)]
+        check(lib.fdlp_xform_plan_info(self._h, *[ctypes.byref(x) for x in v]))
+        self.in_dim, self.out_dim, self.mat_cols, self.tile, self.lds_bytes = [x.value for x in v]
+        self.affine = bool(affine)
+
+    def close(self):
+        h = getattr(self, "_h", None)
+        if h:
+            lib.fdlp_xform_plan_destroy(h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    def compute(self, feats: torch.Tensor, lengths: Sequence[int], mats: torch.Tensor,
+                mat_index: Optional[Sequence[int]] = None, norm: Optional[torch.Tensor] = None,
+                norm_index: Optional[Sequence[int]] = None, norm_vars: bool = True,
+                offsets: Optional[Sequence[int]] = None, out: Optional[torch.Tensor] = None, stream=None) -> torch.Tensor:
+        """feats, lengths, norm, norm_index, norm_vars, offsets as for PostPlan.compute; mats: float32 device tensor
+        [out_dim, mat_cols] or [n, out_dim, mat_cols], mat_index[u] the matrix of utterance u (None: matrix 0).
+        Returns out [rows, out_dim]."""
+        b, out, keep = _make_batch("XformPlan.compute", self.cfg.dim, self.out_dim, feats, lengths, norm, norm_index,
+                                   norm_vars, offsets, out)
+        if not isinstance(mats, torch.Tensor) or mats.dtype != torch.float32 or mats.device != feats.device:
+            raise ValueError("XformPlan.compute: mats must be a float32 tensor on the features' device")
+        if mats.dim() == 2:
+            mats = mats.unsqueeze(0)
+        if mats.dim() != 3 or mats.shape[0] < 1 or tuple(mats.shape[1:]) != (self.out_dim, self.mat_cols):
+            raise ValueError("XformPlan.compute: mats must be [%d, %d] or [n, %d, %d], got %s"
+                             % (self.out_dim, self.mat_cols, self.out_dim, self.mat_cols, tuple(mats.shape)))
+        mats = mats.contiguous()
+        midx = None
+        if mat_index is not None:
+            midx = np.ascontiguousarray(np.asarray(mat_index, dtype=np.int32))
+            if midx.size != b.n_utt:
+                raise ValueError("one matrix index per utterance")
+        s = stream if stream is not None else torch.cuda.current_stream(feats.device)
+        check(lib.fdlp_xform_compute(self._h, ctypes.byref(b), ctypes.c_void_p(mats.data_ptr()), mats.shape[0],
+                                     ptr(midx, ctypes.c_int32) if midx is not None else None,
+                                     ctypes.c_void_p(s.cuda_stream)))
         return out
 
 
@@ -223,6 +295,36 @@ def read_dmatrix_table(rspecifier: str):
                 cur.close()
 
 
+def read_kaldi_matrix(path: str) -> np.ndarray:
+    """A Kaldi matrix *file* (final.mat, an fMLLR matrix) as float32: binary "FM ", binary "DM " (rounded to float32
+    once) or the text form " [ ... ]" with one row per line."""
+    raw = open(path, "rb").read()
+    if raw[:2] == b"\0B":
+        tok = raw[2:5]
+        if tok not in (b"FM ", b"DM "):
+            raise ValueError("%s: not a float or double matrix" % path)
+        if len(raw) < 15 or raw[5] != 4 or raw[10] != 4:
+            raise ValueError("%s: bad matrix dimensions" % path)
+        r, c = struct.unpack("<i", raw[6:10])[0], struct.unpack("<i", raw[11:15])[0]
+        dt = np.dtype("<f4" if tok == b"FM " else "<f8")
+        if r < 0 or c < 0 or len(raw) < 15 + dt.itemsize * r * c:
+            raise ValueError("%s: truncated matrix (%d x %d expected)" % (path, r, c))
+        return np.frombuffer(raw[15:15 + dt.itemsize * r * c], dtype=dt).reshape(r, c).astype(np.float32)
+    try:
+        txt = raw.decode("ascii").strip()
+    except UnicodeDecodeError:
+        raise ValueError("%s: not a Kaldi matrix" % path)
+    if not (txt.startswith("[") and txt.endswith("]")):
+        raise ValueError("%s: not a Kaldi matrix, or a truncated one" % path)
+    try:
+        rows = [[float(v) for v in l.split()] for l in txt[1:-1].split("\n") if l.strip()]
+    except ValueError:
+        raise ValueError("%s: not a Kaldi matrix" % path)
+    if len(set(len(r) for r in rows)) > 1:
+        raise ValueError("%s: rows of different lengths" % path)
+    return np.array(rows, dtype=np.float64).reshape(len(rows), -1).astype(np.float32)
+
+
 def read_utt2spk(rspecifier: str) -> dict:
     _, _, path = _split_specifier(rspecifier)
     out = {}
@@ -293,17 +395,24 @@ class _Slot:
         self.rows = rows
         self.keys, self.lens, self.norm_idx, self.norms = [], [], [], []
         self.where = {}  # stats key -> row of this batch's norm table
+        self.mat_idx, self.mats, self.mwhere = [], [], {}  # the same for the transform table
         self.fill = 0
         self.done = None
 
 
 class PostRunner:
     """opts: the PostConfig fields but dim (taken from the first matrix); stats: None, a [2, D+1] matrix (global)
-    or a dict key -> matrix with utt2spk (None: looked up by the utterance id)."""
+    or a dict key -> matrix with utt2spk (None: looked up by the utterance id).  transform: None, one [N, C] matrix
+    (global) or a dict key -> matrix looked up like the stats (the same utt2spk); the plan is made from the first
+    usable matrix (C = K or K + 1 for the K columns the other stages give), and a matrix of another shape later
+    on is an error for its utterances."""
 
     def __init__(self, opts: dict, stats=None, utt2spk=None, norm_means=True, norm_vars=False, reverse=False,
-                 skip_dims=(), device=0, batch_rows=16384, max_out_bytes=256 << 20, prog="post-feats", log=None):
+                 skip_dims=(), device=0, batch_rows=16384, max_out_bytes=256 << 20, prog="post-feats", log=None,
+                 transform=None):
         self.opts, self.stats, self.utt2spk = opts, stats, utt2spk
+        self.transform = transform
+        self._mat_cache = {}
         self.cmvn = dict(norm_means=norm_means, norm_vars=norm_vars, reverse=reverse, skip_dims=tuple(skip_dims))
         if norm_vars and not norm_means:
             raise ValueError("You cannot normalize the variance but not the mean.")
@@ -333,10 +442,42 @@ class PostRunner:
         v = self._norm_cache[key]
         return None if v is None else (key, v)
 
+    def _mat_for(self, utt):
+        """(cache key, float32 [N, C]) or None (after the warning) when the utterance has no usable transform."""
+        if isinstance(self.transform, dict):
+            key = utt if self.utt2spk is None else self.utt2spk.get(utt)
+            if key is None or key not in self.transform:
+                self.log("No fMLLR transform available for utterance %s, producing no output for this utterance" % utt)
+                return None
+            m = self.transform[key]
+        else:
+            key, m = "", self.transform
+        if key not in self._mat_cache:
+            m = np.ascontiguousarray(m, dtype=np.float32)   # a double matrix is rounded once
+            ok = m.ndim == 2 and m.shape[0] >= 1 and m.shape[1] in (self.in_dim, self.in_dim + 1)
+            if ok and self.xshape is None:
+                self.xshape = m.shape
+            self._mat_cache[key] = m if ok and m.shape == self.xshape else m.shape
+        m = self._mat_cache[key]
+        if isinstance(m, tuple):
+            want = "%d or %d" % (self.in_dim, self.in_dim + 1) if self.xshape is None else "%d x %d" % self.xshape
+            self.log("Transform matrix for utterance %s has bad dimension %s versus feat dim %d (need %s)"
+                     % (utt, " x ".join(str(v) for v in m), self.in_dim, want))
+            return None
+        return key, m
+
     def _setup(self, dim):
         self.dim = dim
+        cfg = PostConfig(dim=dim, **self.opts)
+        if self.transform is not None:       # the device plan waits for the first usable matrix
+            self.in_dim, self.xshape = PostPlan(cfg, -1).out_dim, None
+            return
+        self._make_plan(PostPlan(cfg, self.device))
+
+    def _make_plan(self, plan):
+        dim = self.dim
         torch.cuda.set_device(self.device)
-        self.plan = PostPlan(PostConfig(dim=dim, **self.opts), self.device)
+        self.plan = plan
         rows = max(1, min(self.batch_rows, self.max_out_bytes // (4 * self.plan.out_dim)))
         self.rows = rows
         self.slots = [_Slot(rows, dim, self.plan.out_dim, torch.device("cuda", self.device)) for _ in range(2)]
@@ -349,8 +490,12 @@ class PostRunner:
         if self.apply_norm:
             norm = torch.from_numpy(np.stack(sl.norms)).to(d_in.device)
             idx = sl.norm_idx
-        self.plan.compute(d_in, sl.lens, norm=norm, norm_index=idx, out=sl.d_out,
-                          norm_vars=self.cmvn["norm_vars"])
+        if self.transform is not None:
+            self.plan.compute(d_in, sl.lens, torch.from_numpy(np.stack(sl.mats)).to(d_in.device), sl.mat_idx,
+                              norm=norm, norm_index=idx, out=sl.d_out, norm_vars=self.cmvn["norm_vars"])
+        else:
+            self.plan.compute(d_in, sl.lens, norm=norm, norm_index=idx, out=sl.d_out,
+                              norm_vars=self.cmvn["norm_vars"])
         sl.h_out[:n].copy_(sl.d_out[:n], non_blocking=True)
         sl.done = torch.cuda.Event()
         sl.done.record()
@@ -366,11 +511,12 @@ class PostRunner:
             pos += n
             self.num_done += 1
         sl.keys, sl.lens, sl.norm_idx, sl.norms, sl.where, sl.fill, sl.done = [], [], [], [], {}, 0, None
+        sl.mat_idx, sl.mats, sl.mwhere = [], [], {}
 
     def run(self, rspecifier: str, writer: FeatWriter):
         cur = 0
         for utt, m in MatReader(rspecifier):
-            if self.plan is None and m.shape[0] > 0:
+            if self.dim is None and m.shape[0] > 0:
                 self._setup(m.shape[1])
             if m.shape[0] == 0 or m.shape[1] != self.dim:
                 self.log("Empty or mismatched feature matrix for utterance %s (%d x %d)" % (utt, m.shape[0], m.shape[1]))
@@ -384,6 +530,16 @@ class PostRunner:
                              "utterance" % utt)
                     self.num_err += 1
                     continue
+            mv = None
+            if self.transform is not None:
+                mv = self._mat_for(utt)
+                if mv is None:
+                    self.num_err += 1
+                    continue
+                if self.plan is None:
+                    N, C = mv[1].shape
+                    self._make_plan(XformPlan(PostConfig(dim=self.dim, **self.opts), N, C == self.in_dim + 1,
+                                              self.device))
             sl = self.slots[cur]
             if sl.fill and sl.fill + m.shape[0] > sl.rows:
                 self._launch(sl)
@@ -403,6 +559,12 @@ class PostRunner:
                     sl.where[key] = len(sl.norms)
                     sl.norms.append(vec)
                 sl.norm_idx.append(sl.where[key])
+            if mv is not None:
+                key, mat = mv
+                if key not in sl.mwhere:
+                    sl.mwhere[key] = len(sl.mats)
+                    sl.mats.append(mat)
+                sl.mat_idx.append(sl.mwhere[key])
         if self.slots:
             if self.slots[cur].fill:
                 self._launch(self.slots[cur])
@@ -479,12 +641,30 @@ def splice_feats_parser():
     return ap
 
 
+def transform_feats_parser():
+    ap = argparse.ArgumentParser(
+        prog="transform-feats", description="Apply transform (e.g. LDA; HLDA; fMLLR/CMLLR; MLLT/STC) (on the MI355X). "
+        "Linear transform if transform-num-cols == feature-dim, affine if transform-num-cols == feature-dim+1 "
+        "(->append 1.0 to features). Per-utterance by default, or per-speaker if utt2spk option provided. "
+        "Global if transform-rxfilename provided. Usage: transform-feats [options] "
+        "(<transform-rspecifier>|<transform-rxfilename>) <feats-rspecifier> <feats-wspecifier>")
+    ap.add_argument("--utt2spk", default="", help="rspecifier for utterance to speaker map")
+    _add_common(ap)
+    ap.add_argument("transform")
+    ap.add_argument("feats")
+    ap.add_argument("out")
+    return ap
+
+
 def post_feats_parser():
-    """apply-cmvn | add-deltas | splice-feats in one launch per batch; every stage is off by default."""
-    ap = argparse.ArgumentParser(prog="post-feats", description="apply-cmvn | add-deltas | splice-feats fused into one "
-                                 "kernel launch per batch (on the MI355X). Usage: post-feats [options] "
-                                 "<feats-rspecifier> <feats-wspecifier>")
+    """apply-cmvn | add-deltas | splice-feats | transform-feats in one launch per batch; every stage is off by
+    default."""
+    ap = argparse.ArgumentParser(prog="post-feats", description="apply-cmvn | add-deltas | splice-feats | "
+                                 "transform-feats fused into one kernel launch per batch (on the MI355X). Usage: "
+                                 "post-feats [options] <feats-rspecifier> <feats-wspecifier>")
     ap.add_argument("--cmvn", default="", help="CMVN stats: a table rspecifier or the file of one global matrix")
+    ap.add_argument("--transform", default="", help="transform-feats as the last stage: the file of one global "
+                    "matrix (final.mat) or a table rspecifier (per utterance, per speaker with --utt2spk)")
     _add_cmvn_opts(ap)
     _add_delta_opts(ap, 0)
     _add_splice_opts(ap, 0)
@@ -501,11 +681,22 @@ def _load_stats(arg: str):
     return dict(read_dmatrix_table(arg))
 
 
-def _run(prog, a, opts, cmvn_arg=None):
+def _load_transform(arg: str):
+    kind, _, _ = _split_specifier(arg)
+    if kind is None:
+        return read_kaldi_matrix(arg)
+    return dict(read_dmatrix_table(arg))
+
+
+def _run(prog, a, opts, cmvn_arg=None, transform_arg=None):
     stats = utt2spk = None
     kw = {}
+    if transform_arg:
+        kw["transform"] = _load_transform(transform_arg)
+        if a.utt2spk:
+            utt2spk = read_utt2spk(a.utt2spk)
     if cmvn_arg:
-        kw = dict(norm_means=a.norm_means, norm_vars=a.norm_vars, reverse=a.reverse, skip_dims=a.skip_dims)
+        kw.update(norm_means=a.norm_means, norm_vars=a.norm_vars, reverse=a.reverse, skip_dims=a.skip_dims)
         if a.norm_vars and not a.norm_means:
             print("ERROR (%s) You cannot normalize the variance but not the mean." % prog, file=sys.stderr)
             return 1
@@ -522,8 +713,11 @@ def _run(prog, a, opts, cmvn_arg=None):
     writer.close()
     what = {"apply-cmvn": "Applied cepstral mean %snormalization" % ("and variance " if kw.get("norm_vars") else ""),
             "add-deltas": "Added deltas", "splice-feats": "Spliced features",
-            "post-feats": "Applied the feature post-processing chain"}[prog]
-    print("LOG (%s) %s to %d utterances, errors on %d" % (prog, what, done, err), file=sys.stderr)
+            "post-feats": "Applied the feature post-processing chain", "transform-feats": "Applied transform"}[prog]
+    if prog == "transform-feats":
+        print("LOG (%s) Applied transform to %d utterances; %d had errors." % (prog, done, err), file=sys.stderr)
+    else:
+        print("LOG (%s) %s to %d utterances, errors on %d" % (prog, what, done, err), file=sys.stderr)
     return 0 if done else 1
 
 
@@ -546,11 +740,16 @@ def main_post_feats(argv=None):
     a = post_feats_parser().parse_args(argv)
     opts = dict(truncate=a.truncate, delta_order=a.delta_order, delta_window=a.delta_window,
                 left_context=a.left_context, right_context=a.right_context)
-    return _run("post-feats", a, opts, a.cmvn or None)
+    return _run("post-feats", a, opts, a.cmvn or None, a.transform or None)
+
+
+def main_transform_feats(argv=None):
+    a = transform_feats_parser().parse_args(argv)
+    return _run("transform-feats", a, {}, None, a.transform)
 
 
 MAINS = {"apply-cmvn": main_apply_cmvn, "add-deltas": main_add_deltas, "splice-feats": main_splice_feats,
-         "post-feats": main_post_feats}
+         "post-feats": main_post_feats, "transform-feats": main_transform_feats}
 
 if __name__ == "__main__":
     if len(sys.argv) < 2 or sys.argv[1] not in MAINS:
