@@ -409,6 +409,54 @@ int fdlp_xform_plan_info(const fdlp_xform_plan* plan, int32_t* in_dim, int32_t* 
  * per-speaker fMLLR shares the launch. */
 int fdlp_xform_compute(fdlp_xform_plan* plan, const fdlp_post_batch* batch, const void* mat_dev, int32_t n_mat,
                        const int32_t* mat_index, void* stream);
+
+/* ---- extract-posterior: the feed-forward acoustic model after the chain --------------------- */
+/* nnetFeedforward of the reference (src/nnet/nnet_models.py:9-31; extract_posterior.py, compute_per_utt_fer.py):
+ * n_linear nn.Linear layers with ReLU between them, on the rows the stages of `post` give.  With x_0 the row
+ * (width dims[0]) and W_l [dims[l+1], dims[l]], b_l [dims[l+1]] in nn.Linear's layout:
+ *     y_l = f_l(x_l) W_l^T + b_l,   f_0 the identity, f_l = max(x, 0) for l > 0,   x_{l+1} = y_l
+ * so every layer stores its PRE-activation, which is what the reference taps (embeds.append before the ReLU).
+ * Layer 0 runs in the chain's own kernel launch as an affine transform ([W_0 | b_0], xform_kernel: the spliced
+ * rows never reach HBM); the others in dense_kernel (fdlp_nnet.hip) on v_mfma_f32_32x32x2_f32, exact float32.
+ * Each y_l[n] of a dense layer is one chain acc = fmaf(f(x[k]), W[n][k], acc) from acc = +0 over
+ *     for g = 0, 8, 16, .. < ceil(K / 32) 32:  for i = 0 .. 3:  k = g + i, then k = g + 4 + i
+ * (a k >= K contributes fmaf(+0, +0, acc)), then one float32 add of b[n]; layer 0 follows the order documented
+ * for fdlp_xform_config.  Both are functions of K alone: a row's bits do not depend on the batch, on the row's
+ * position or on the rows beside it.
+ * The row epilogue, on the last layer's logits x [C] with m = max_j x_j and S = sum_j exp(x_j - m):
+ *     FDLP_NNET_SOFTMAX  p_j = exp(x_j - m) / S   (extract_posterior.py --add_softmax; the reference's
+ *                        np.exp(X) / sum has no max subtraction and gives NaN above 88: that is not reproduced)
+ *     FDLP_NNET_LOGLIKE  ((x_j - m) - log S) - prior_weight * prior[j]   (log_softmax - prior_weight * prior of
+ *                        dump_genclassifier_outputs.py:110, what latgen-faster-mapped consumes) */
+#define FDLP_NNET_MAX_LINEAR 32
+enum { FDLP_NNET_RAW = 0, FDLP_NNET_SOFTMAX = 1, FDLP_NNET_LOGLIKE = 2 };
+typedef struct fdlp_nnet_config {
+  fdlp_post_config post;                    /* the stages before the network (post.device is the plan's device) */
+  int32_t n_linear;                         /* linear layers: 1 .. FDLP_NNET_MAX_LINEAR                          */
+  int32_t dims[FDLP_NNET_MAX_LINEAR + 1];   /* dims[0] = the stages' out_dim, dims[l+1] = outputs of layer l     */
+} fdlp_nnet_config;
+typedef struct fdlp_nnet_plan fdlp_nnet_plan;
+/* weights[l] / biases[l]: host float32 [dims[l+1], dims[l]] / [dims[l+1]], copied to the device (the plan owns the
+ * copies; both may be NULL for a host-only plan).  The plan allocates two [max_rows, max hidden width] float32
+ * workspaces the layers ping-pong between (none with one layer).  FDLP_E_INVALID with the sizes in the message for
+ * n_linear outside its range, a dimension < 1, dims[0] different from the stages' out_dim, max_rows < 1, or a
+ * layer 0 that does not fit the LDS beside the chain's tile. */
+int fdlp_nnet_plan_create(const fdlp_nnet_config* cfg, const float* const* weights, const float* const* biases,
+                          int64_t max_rows, fdlp_nnet_plan** out);
+int fdlp_nnet_plan_destroy(fdlp_nnet_plan* plan);
+/* in_dim = dims[0]; n_linear; out_dims[n_linear] = dims[1 ..]; bytes of the two workspaces together; tile[3] = row
+ * tile, column tile and k chunk of dense_kernel; its LDS bytes at the full column tile.  Works on a host-only plan.
+ * Any pointer may be NULL. */
+int fdlp_nnet_plan_info(const fdlp_nnet_plan* plan, int32_t* in_dim, int32_t* n_linear, int32_t* out_dims,
+                        int64_t* workspace_bytes, int32_t* tile, int32_t* lds_bytes);
+/* `batch` as for fdlp_post_compute (n_rows <= max_rows, else FDLP_E_CAPACITY).  tap 0: the last layer's output;
+ * tap l in 1 .. n_linear - 1: the pre-activation of hidden layer n_linear - l (counted from 1), the reference's
+ * embeds[-l].  out_dev is [n_rows, width of the tapped layer]; layers after the tap are not computed.  mode: raw,
+ * or with tap 0 softmax / loglike; loglike needs prior_dev (device float32 [C]).  Rows of the batch that belong to
+ * no utterance are left alone when layer 0 is tapped and hold unspecified values otherwise. */
+int fdlp_nnet_compute(fdlp_nnet_plan* plan, const fdlp_post_batch* batch, int32_t tap, int32_t mode,
+                      const void* prior_dev, float prior_weight, void* stream);
+
 /* ApplyCmvn / ApplyCmvnReverse as two float32 vectors: out[0 .. dim) = scale, out[dim .. 2 dim) = offset, from the
  * [2, dim + 1] double stats compute-cmvn-stats writes (count = stats[dim]; count < 1 is FDLP_E_INVALID).
  * mean = s0/count; norm_vars: var = s1/count - mean^2 floored at 1e-20 (a warning on stderr), scale = 1/sqrt(var),

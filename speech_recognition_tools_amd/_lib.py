@@ -102,6 +102,14 @@ class FdlpXformConfigC(ctypes.Structure):
     _fields_ = [("post", FdlpPostConfigC), ("out_dim", c_i32), ("affine", c_i32)]
 
 
+FDLP_NNET_MAX_LINEAR = 32
+FDLP_NNET_RAW, FDLP_NNET_SOFTMAX, FDLP_NNET_LOGLIKE = 0, 1, 2
+
+
+class FdlpNnetConfigC(ctypes.Structure):
+    _fields_ = [("post", FdlpPostConfigC), ("n_linear", c_i32), ("dims", c_i32 * (FDLP_NNET_MAX_LINEAR + 1))]
+
+
 class FdlpPostBatchC(ctypes.Structure):
     _fields_ = [
         ("n_utt", c_i32), ("norm_mul", c_i32), ("in_dev", c_p), ("n_rows", c_i64), ("row_off", P_i64),
@@ -213,6 +221,11 @@ SIGNATURES = {
     "fdlp_xform_plan_destroy": (c_i32, [c_p]),
     "fdlp_xform_plan_info": (c_i32, [c_p, P_i32, P_i32, P_i32, P_i32, P_i32]),
     "fdlp_xform_compute": (c_i32, [c_p, ctypes.POINTER(FdlpPostBatchC), c_p, c_i32, P_i32, c_p]),
+    "fdlp_nnet_plan_create": (c_i32, [ctypes.POINTER(FdlpNnetConfigC), ctypes.POINTER(c_p), ctypes.POINTER(c_p), c_i64,
+                                      ctypes.POINTER(c_p)]),
+    "fdlp_nnet_plan_destroy": (c_i32, [c_p]),
+    "fdlp_nnet_plan_info": (c_i32, [c_p, P_i32, P_i32, P_i32, P_i64, P_i32, P_i32]),
+    "fdlp_nnet_compute": (c_i32, [c_p, ctypes.POINTER(FdlpPostBatchC), c_i32, c_i32, c_p, ctypes.c_float, c_p]),
     "fdlp_cmvn_norm": (c_i32, [P_dbl, c_i32, c_i32, c_i32, c_i32, P_i32, c_i32, ctypes.POINTER(ctypes.c_float)]),
     "fdlp_noise_params_f64": (c_i32, [P_dbl, c_i64, P_i16, c_i64, c_dbl, c_dbl, P_i64, P_dbl]),
     "fdlp_mat_reader_open": (c_i32, [ctypes.c_char_p, ctypes.POINTER(c_p)]),

@@ -259,6 +259,17 @@ size_t xform_ms_bytes(int N);  // LDS bytes of the staged matrix chunk
 size_t xform_lds_bytes(int tf, int D, int order, int window, int L, int R, int N);
 hipError_t checks_post(unsigned int* v, bool reset);
 
+// Feed-forward network after the chain (fdlp_nnet.hip).  dense_kernel: out [rows, N] = f(A [rows, K]) W[N, K]^T + b,
+// f = max(x, 0) with relu, a kDenseTM x dense_col_tile(N) output tile per workgroup, K in chunks of kDenseKC.
+constexpr int kDenseTM = 128, kDenseTN = 128, kDenseKC = 32;
+int dense_col_tile(int N);       // kDenseTN, or 64 for N <= 64
+size_t dense_lds_bytes(int N);   // LDS bytes of a workgroup
+hipError_t launch_dense(const float* A, const float* W, const float* bias, float* out, int64_t rows, int K, int N,
+                        int relu, hipStream_t s);
+// mode 1: softmax, 2: log_softmax - w prior, in place on x [rows, C]; 0: nothing
+hipError_t launch_row_epilogue(float* x, int64_t rows, int C, int mode, const float* prior, float w, hipStream_t s);
+hipError_t checks_nnet(unsigned int* v, bool reset);
+
 // One utterance of a reverb batch (fdlp_reverb): samples at pcm[off, off+T), y at [yoff, yoff+T+R-1).
 struct RevUtt {
   int64_t off, T, yoff, noff;  // noff < 0: no noise mixing

@@ -1261,7 +1261,7 @@ int fdlp_set_debug(fdlp_plan* p, int32_t keep_intermediates) {
 int fdlp_device_checks(int32_t* enabled, uint32_t* violations, uint32_t* last_line, int32_t reset) {
   unsigned int tot = 0, line = 0;
   hipError_t (*const fns[])(unsigned int*, bool) = {fdlp::checks_dct, fdlp::checks_autocorr, fdlp::checks_lpc,
-                                                    fdlp::checks_misc, fdlp::checks_post};
+                                                    fdlp::checks_misc, fdlp::checks_post, fdlp::checks_nnet};
   HIP_TRY(hipDeviceSynchronize());
   for (auto fn : fns) {
     unsigned int v[2] = {0u, 0u};
@@ -2013,6 +2013,191 @@ int fdlp_xform_compute(fdlp_xform_plan* x, const fdlp_post_batch* b, const void*
   fdlp::XformConsts xc{};
   xc.N = x->N; xc.C = x->C; xc.affine = x->affine; xc.n_mat = n_mat;
   return post_compute(x->post, b, stream, &xc, mat_dev, mat_index);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Network plan (cmvn | deltas | splice | nnetFeedforward): a transform plan for layer 0 ([W_0 | b_0], affine),
+// the other layers' weights on the device, and two workspaces the dense layers ping-pong between
+// ---------------------------------------------------------------------------------------------
+struct fdlp_nnet_plan {
+  fdlp_xform_plan* l0 = nullptr;
+  int n_linear = 0, device = -1;
+  std::vector<int> dims;        // n_linear + 1
+  int64_t max_rows = 0;
+  int max_hidden = 0;           // widest of dims[1 .. n_linear - 1], 0 with one layer
+  float* d_m0 = nullptr;        // [dims[1], dims[0] + 1]
+  std::vector<float*> d_w, d_b; // layers 1 ..; entry 0 unused
+  float* d_ws[2] = {nullptr, nullptr};
+};
+
+static int free_nnet_plan(fdlp_nnet_plan* p) {
+  if (!p) return FDLP_OK;
+  int rc = FDLP_OK;
+  {
+    DeviceGuard dg(p->device);
+    if (p->d_m0) (void)hipFree(p->d_m0);
+    for (float* w : p->d_w)
+      if (w) (void)hipFree(w);
+    for (float* b : p->d_b)
+      if (b) (void)hipFree(b);
+    for (float* w : p->d_ws)
+      if (w) (void)hipFree(w);
+    if (p->l0) rc = fdlp_xform_plan_destroy(p->l0);
+  }
+  delete p;
+  return rc;
+}
+
+int fdlp_nnet_plan_create(const fdlp_nnet_config* cfg, const float* const* weights, const float* const* biases,
+                          int64_t max_rows, fdlp_nnet_plan** out) {
+  if (!cfg || !out) return fail(FDLP_E_INVALID, "fdlp_nnet_plan_create: null argument");
+  *out = nullptr;
+  const int nl = cfg->n_linear;
+  if (nl < 1 || nl > FDLP_NNET_MAX_LINEAR)
+    return fail(FDLP_E_INVALID, "the network needs 1 .. " + std::to_string(FDLP_NNET_MAX_LINEAR) +
+                                    " linear layers, got n_linear = " + std::to_string(nl));
+  std::string shape;
+  for (int l = 0; l <= nl; ++l) shape += (l ? " -> " : "") + std::to_string(cfg->dims[l]);
+  for (int l = 0; l <= nl; ++l)
+    if (cfg->dims[l] < 1)
+      return fail(FDLP_E_INVALID, "network dimension " + std::to_string(l) + " is " + std::to_string(cfg->dims[l]) +
+                                      " (every dimension must be >= 1; dims " + shape + ")");
+  if (max_rows < 1) return fail(FDLP_E_INVALID, "max_rows must be >= 1, got " + std::to_string(max_rows));
+  const bool dev = cfg->post.device >= 0;
+  if (dev && (!weights || !biases)) return fail(FDLP_E_INVALID, "fdlp_nnet_plan_create: null weights or biases");
+  for (int l = 0; dev && l < nl; ++l)
+    if (!weights[l] || !biases[l])
+      return fail(FDLP_E_INVALID, "fdlp_nnet_plan_create: null weights or biases of layer " + std::to_string(l));
+  auto* p = new (std::nothrow) fdlp_nnet_plan;
+  if (!p) return fail(FDLP_E_NOMEM, "out of memory");
+  p->n_linear = nl;
+  p->device = cfg->post.device;
+  p->dims.assign(cfg->dims, cfg->dims + nl + 1);
+  p->max_rows = max_rows;
+  for (int l = 1; l < nl; ++l) p->max_hidden = std::max(p->max_hidden, cfg->dims[l]);
+  p->d_w.assign((size_t)nl, nullptr);
+  p->d_b.assign((size_t)nl, nullptr);
+  int rc;
+#define NNET_FAIL(code, msg) do { rc = fail(code, msg); free_nnet_plan(p); return rc; } while (0)
+#define NNET_TRY(expr)                           \
+  do {                                           \
+    rc = (expr);                                 \
+    if (rc != FDLP_OK) {                         \
+      std::string m_ = fdlp::last_error_slot();  \
+      free_nnet_plan(p);                         \
+      fdlp::last_error_slot() = m_;              \
+      return rc;                                 \
+    }                                            \
+  } while (0)
+  fdlp_xform_config xc{};
+  xc.post = cfg->post;
+  xc.out_dim = cfg->dims[1];
+  xc.affine = 1;
+  NNET_TRY(fdlp_xform_plan_create(&xc, &p->l0));
+  const int K0 = p->l0->post->Dout;
+  if (K0 != cfg->dims[0])
+    NNET_FAIL(FDLP_E_INVALID, "the network's input dimension dims[0] = " + std::to_string(cfg->dims[0]) +
+                                  " differs from the " + std::to_string(K0) + " columns the stages before it give");
+  if (!dev) {
+    *out = p;
+    return FDLP_OK;
+  }
+  DeviceGuard dg(p->device);
+  if (dg.status() != hipSuccess) NNET_FAIL(FDLP_E_HIP, "hipSetDevice failed");
+  {
+    // layer 0 as transform-feats' affine matrix: [W_0 | b_0]
+    const int H = cfg->dims[1];
+    std::vector<float> m0((size_t)H * (K0 + 1));
+    for (int n = 0; n < H; ++n) {
+      memcpy(&m0[(size_t)n * (K0 + 1)], weights[0] + (size_t)n * K0, sizeof(float) * K0);
+      m0[(size_t)n * (K0 + 1) + K0] = biases[0][n];
+    }
+    NNET_TRY(upload(&p->d_m0, m0.data(), m0.size()));
+  }
+  for (int l = 1; l < nl; ++l) {
+    NNET_TRY(upload(&p->d_w[(size_t)l], weights[l], (size_t)cfg->dims[l + 1] * cfg->dims[l]));
+    NNET_TRY(upload(&p->d_b[(size_t)l], biases[l], (size_t)cfg->dims[l + 1]));
+  }
+  if (p->max_hidden > 0) {
+    const size_t n = (size_t)max_rows * p->max_hidden;
+    for (float*& w : p->d_ws) {
+      if (hipMalloc((void**)&w, sizeof(float) * n) != hipSuccess) {
+        w = nullptr;
+        NNET_FAIL(FDLP_E_NOMEM, "network workspace allocation failed: 2 x " + std::to_string(max_rows) + " rows x " +
+                                    std::to_string(p->max_hidden) + " columns of float32");
+      }
+      // rows no utterance covers are read by the dense layers (and never stored into an utterance's rows)
+      if (hipMemset(w, 0, sizeof(float) * n) != hipSuccess) NNET_FAIL(FDLP_E_HIP, "network workspace memset failed");
+    }
+  }
+#undef NNET_TRY
+#undef NNET_FAIL
+  *out = p;
+  return FDLP_OK;
+}
+
+int fdlp_nnet_plan_destroy(fdlp_nnet_plan* p) { return free_nnet_plan(p); }
+
+int fdlp_nnet_plan_info(const fdlp_nnet_plan* p, int32_t* in_dim, int32_t* n_linear, int32_t* out_dims,
+                        int64_t* workspace_bytes, int32_t* tile, int32_t* lds_bytes) {
+  if (!p) return fail(FDLP_E_INVALID, "fdlp_nnet_plan_info: null plan");
+  if (in_dim) *in_dim = p->dims[0];
+  if (n_linear) *n_linear = p->n_linear;
+  if (out_dims)
+    for (int l = 0; l < p->n_linear; ++l) out_dims[l] = p->dims[(size_t)l + 1];
+  if (workspace_bytes) *workspace_bytes = 2 * (int64_t)sizeof(float) * p->max_rows * p->max_hidden;
+  if (tile) {
+    tile[0] = fdlp::kDenseTM;
+    tile[1] = fdlp::kDenseTN;
+    tile[2] = fdlp::kDenseKC;
+  }
+  if (lds_bytes) *lds_bytes = (int32_t)fdlp::dense_lds_bytes(fdlp::kDenseTN);
+  return FDLP_OK;
+}
+
+int fdlp_nnet_compute(fdlp_nnet_plan* p, const fdlp_post_batch* b, int32_t tap, int32_t mode, const void* prior_dev,
+                      float prior_weight, void* stream) {
+  if (!p || !b) return fail(FDLP_E_INVALID, "fdlp_nnet_compute: null argument");
+  if (p->device < 0) return fail(FDLP_E_INVALID, "fdlp_nnet_compute: host-only plan");
+  if (tap < 0 || tap >= p->n_linear)
+    return fail(FDLP_E_INVALID, "tap " + std::to_string(tap) + " is outside 0 .. " + std::to_string(p->n_linear - 1) +
+                                    " (the network has " + std::to_string(p->n_linear - 1) + " hidden layers)");
+  if (mode != FDLP_NNET_RAW && mode != FDLP_NNET_SOFTMAX && mode != FDLP_NNET_LOGLIKE)
+    return fail(FDLP_E_INVALID, "fdlp_nnet_compute: unknown mode " + std::to_string(mode));
+  if (mode != FDLP_NNET_RAW && tap != 0)
+    return fail(FDLP_E_INVALID, "softmax and loglike apply to the last layer only (tap 0), got tap " +
+                                    std::to_string(tap));
+  if (mode == FDLP_NNET_LOGLIKE && (!prior_dev || ((uintptr_t)prior_dev & 3u)))
+    return fail(FDLP_E_INVALID, "loglike needs a 4-byte aligned device prior vector");
+  if (b->n_rows > p->max_rows)
+    return fail(FDLP_E_CAPACITY, "batch of " + std::to_string(b->n_rows) + " rows exceeds the plan's max_rows " +
+                                     std::to_string(p->max_rows));
+  if (b->n_utt > 0 && (!b->out_dev || ((uintptr_t)b->out_dev & 3u)))
+    return fail(FDLP_E_INVALID, "fdlp_nnet_compute: out_dev must be a 4-byte aligned device pointer");
+  const int last = p->n_linear - 1 - tap;  // the tapped layer
+  hipStream_t s = (hipStream_t)stream;
+  // layer 0 in the chain's launch; its batch checks are the chain's
+  fdlp_post_batch b0 = *b;
+  if (last > 0) b0.out_dev = p->d_ws[0];
+  fdlp::XformConsts xc{};
+  xc.N = p->dims[1]; xc.C = p->dims[0] + 1; xc.affine = 1; xc.n_mat = 1;
+  {
+    const int rc = post_compute(p->l0->post, &b0, stream, &xc, p->d_m0, nullptr);
+    if (rc != FDLP_OK) return rc;
+  }
+  if (b->n_utt == 0 || b->n_rows == 0) return FDLP_OK;
+  DeviceGuard dg(p->device);
+  HIP_TRY(dg.status());
+  for (int l = 1; l <= last; ++l) {
+    const float* in = p->d_ws[(l - 1) & 1];
+    float* o = l == last ? (float*)b->out_dev : p->d_ws[l & 1];
+    HIP_TRY(fdlp::launch_dense(in, p->d_w[(size_t)l], p->d_b[(size_t)l], o, b->n_rows, p->dims[(size_t)l],
+                               p->dims[(size_t)l + 1], 1, s));
+  }
+  if (mode != FDLP_NNET_RAW)
+    HIP_TRY(fdlp::launch_row_epilogue((float*)b->out_dev, b->n_rows, p->dims[(size_t)p->n_linear], mode,
+                                      (const float*)prior_dev, prior_weight, s));
+  return FDLP_OK;
 }
 
 int fdlp_reverb(const fdlp_reverb_batch* b, void* stream) {
