@@ -457,6 +457,70 @@ int fdlp_nnet_plan_info(const fdlp_nnet_plan* plan, int32_t* in_dim, int32_t* n_
 int fdlp_nnet_compute(fdlp_nnet_plan* plan, const fdlp_post_batch* batch, int32_t tap, int32_t mode,
                       const void* prior_dev, float prior_weight, void* stream);
 
+/* ---- dump-genclassifier-outputs: GRU acoustic models after the chain -------------------------- */
+/* The recurrent models of the reference's hybrid recipes (src/nnet/nnet_models.py nnetRNN and the classifier
+ * branch of nnetAEClassifierMultitask; dump_genclassifier_outputs.py) as a list of stages on the rows the stages
+ * of `post` give.  Stage s maps rows of width dims[s] to rows of width dims[s+1]:
+ *   FDLP_RNN_GRU          nn.GRU (one layer, gate order r, z, n): W_ih [3H, K], W_hh [3H, H], b_ih, b_hh [3H]
+ *   FDLP_RNN_LINEAR       y = x W^T + b, W [N, K] (a Conv1d of kernel size 1, squeezed)
+ *   FDLP_RNN_LINEAR_RELU  the same; the ReLU is applied when the NEXT stage loads the output, so a tap gives the
+ *                         pre-activation (the encoder's bottleneck)
+ * A GRU stage is two launches: the input projection G = x W_ih^T + b_ih of all rows at once (stage 0: inside the
+ * chain's launch as the affine transform [W_ih | b_ih], so the spliced rows never reach HBM; later stages:
+ * dense_kernel, its chain order above), then gru_scan_kernel (fdlp_nnet.hip), one workgroup per group of up to
+ * group_utts = 32 utterances, which are the M dimension of v_mfma_f32_32x32x2_f32.  Per utterance, h_{-1} = 0 and
+ *     acc_c[j] = the chain fmaf(h_{t-1}[k], W_hh[c H + j][k], acc) from acc = +0 over
+ *                for g = 0, 8, 16, .. < ceil(H / 16) 16:  for i = 0 .. 3:  k = g + i, then k = g + 4 + i
+ *                (a k >= H contributes fmaf(+0, +0, acc)),  c = r, z, n
+ *     a_r = G_r[t][j] + (acc_r[j] + b_hr[j])          r = 1 / (1 + exp(-a_r))        and z likewise
+ *     a_n = G_n[t][j] + r (acc_n[j] + b_hn[j])        n = tanh(a_n)
+ *     h_t[j] = (1 - z) n + z h_{t-1}[j]
+ * every operation rounded to float32 as written, exp and tanh the device library's float32 functions, the division
+ * correctly rounded.  Order and operations depend on H alone, so an utterance's bits do not depend on its group,
+ * its slot, the other utterances' lengths or the batch.  Utterances are sorted by length (descending, stable) and
+ * cut into groups of group_utts; a workgroup walks t up to the longest length of its group and depends on no other
+ * workgroup.  Sizing: a step of a full group is 2 x 32 x 3H x H flop of float32 MFMA and re-reads the 12 H^2 bytes
+ * of W_hh from L2; a batch of n utterances keeps ceil(n / 32) CUs busy; H is limited by the 160 KB LDS (two
+ * [32, H] state buffers beside the W_hh chunks) to 384. */
+#define FDLP_RNN_MAX_STAGES 32
+enum { FDLP_RNN_GRU = 0, FDLP_RNN_LINEAR = 1, FDLP_RNN_LINEAR_RELU = 2 };
+typedef struct fdlp_rnn_config {
+  fdlp_post_config post;                    /* the stages before the model (post.device is the plan's device)   */
+  int32_t n_stages;                         /* 1 .. FDLP_RNN_MAX_STAGES                                          */
+  int32_t kind[FDLP_RNN_MAX_STAGES];
+  int32_t dims[FDLP_RNN_MAX_STAGES + 1];    /* dims[0] = the post stages' out_dim, dims[s+1] = outputs of stage s */
+} fdlp_rnn_config;
+typedef struct fdlp_rnn_plan fdlp_rnn_plan;
+/* params: 4 host float32 pointers per stage, {w_ih, w_hh, b_ih, b_hh} for a GRU and {w, NULL, b, NULL} otherwise,
+ * copied to the device (may be NULL for a host-only plan).  The plan allocates one [max_rows, 3 max H] buffer for G
+ * (max H over the GRU stages), two [max_rows, widest of dims[1 .. n_stages - 1]] buffers the stages ping-pong
+ * between, and the group table of ceil(max_utts / 32) groups of 32 slots of 16 bytes.  FDLP_E_INVALID with the
+ * numbers in the message for n_stages outside its range, an unknown kind, a dimension < 1, dims[0] different from
+ * the post stages' out_dim, max_rows < 1, max_utts < 1, or a GRU too wide for the LDS. */
+int fdlp_rnn_plan_create(const fdlp_rnn_config* cfg, const float* const* params, int64_t max_rows, int32_t max_utts,
+                         fdlp_rnn_plan** out);
+int fdlp_rnn_plan_destroy(fdlp_rnn_plan* plan);
+/* in_dim = dims[0]; n_stages; out_dims[n_stages] = dims[1 ..]; the bytes of the workspaces above together;
+ * group_utts = 32; the LDS bytes of gru_scan_kernel at the plan's widest GRU (0 without one).  Works on a host-only
+ * plan.  Any pointer may be NULL. */
+int fdlp_rnn_plan_info(const fdlp_rnn_plan* plan, int32_t* in_dim, int32_t* n_stages, int32_t* out_dims,
+                       int64_t* workspace_bytes, int32_t* group_utts, int32_t* lds_bytes);
+/* The group table of a batch with these lengths (each >= 1): utterance u is slot slot_of[u] of group group_of[u],
+ * *n_groups = ceil(n_utts / 32).  Host only. */
+int fdlp_rnn_plan_groups(const fdlp_rnn_plan* plan, const int32_t* lengths, int32_t n_utts, int32_t* group_of,
+                         int32_t* slot_of, int32_t* n_groups);
+/* `batch` as for fdlp_post_compute, with n_utt <= max_utts (FDLP_E_INVALID), n_rows <= max_rows (FDLP_E_CAPACITY)
+ * and utterances that do not overlap.  tap s: the output of stage n_stages - 1 - s, [n_rows, its width] in out_dev;
+ * later stages are not computed.  mode as for fdlp_nnet_compute (FDLP_NNET_RAW, or with tap 0 SOFTMAX / LOGLIKE).
+ * Rows that belong to no utterance hold unspecified values or are left alone. */
+int fdlp_rnn_compute(fdlp_rnn_plan* plan, const fdlp_post_batch* batch, int32_t tap, int32_t mode,
+                     const void* prior_dev, float prior_weight, void* stream);
+/* Per-kernel times of the plan's computes since the last call, from HIP events recorded around every launch while
+ * `on` (fdlp_rnn_set_profiling): ms[0] the input projections and linear stages, ms[1] the scans.  fdlp_rnn_times
+ * waits for the recorded work. */
+int fdlp_rnn_set_profiling(fdlp_rnn_plan* plan, int32_t on);
+int fdlp_rnn_times(fdlp_rnn_plan* plan, double* ms);
+
 /* ApplyCmvn / ApplyCmvnReverse as two float32 vectors: out[0 .. dim) = scale, out[dim .. 2 dim) = offset, from the
  * [2, dim + 1] double stats compute-cmvn-stats writes (count = stats[dim]; count < 1 is FDLP_E_INVALID).
  * mean = s0/count; norm_vars: var = s1/count - mean^2 floored at 1e-20 (a warning on stderr), scale = 1/sqrt(var),

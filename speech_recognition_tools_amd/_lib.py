@@ -110,6 +110,15 @@ class FdlpNnetConfigC(ctypes.Structure):
     _fields_ = [("post", FdlpPostConfigC), ("n_linear", c_i32), ("dims", c_i32 * (FDLP_NNET_MAX_LINEAR + 1))]
 
 
+FDLP_RNN_MAX_STAGES = 32
+FDLP_RNN_GRU, FDLP_RNN_LINEAR, FDLP_RNN_LINEAR_RELU = 0, 1, 2
+
+
+class FdlpRnnConfigC(ctypes.Structure):
+    _fields_ = [("post", FdlpPostConfigC), ("n_stages", c_i32), ("kind", c_i32 * FDLP_RNN_MAX_STAGES),
+                ("dims", c_i32 * (FDLP_RNN_MAX_STAGES + 1))]
+
+
 class FdlpPostBatchC(ctypes.Structure):
     _fields_ = [
         ("n_utt", c_i32), ("norm_mul", c_i32), ("in_dev", c_p), ("n_rows", c_i64), ("row_off", P_i64),
@@ -226,6 +235,14 @@ SIGNATURES = {
     "fdlp_nnet_plan_destroy": (c_i32, [c_p]),
     "fdlp_nnet_plan_info": (c_i32, [c_p, P_i32, P_i32, P_i32, P_i64, P_i32, P_i32]),
     "fdlp_nnet_compute": (c_i32, [c_p, ctypes.POINTER(FdlpPostBatchC), c_i32, c_i32, c_p, ctypes.c_float, c_p]),
+    "fdlp_rnn_plan_create": (c_i32, [ctypes.POINTER(FdlpRnnConfigC), ctypes.POINTER(c_p), c_i64, c_i32,
+                                     ctypes.POINTER(c_p)]),
+    "fdlp_rnn_plan_destroy": (c_i32, [c_p]),
+    "fdlp_rnn_plan_info": (c_i32, [c_p, P_i32, P_i32, P_i32, P_i64, P_i32, P_i32]),
+    "fdlp_rnn_plan_groups": (c_i32, [c_p, P_i32, c_i32, P_i32, P_i32, P_i32]),
+    "fdlp_rnn_compute": (c_i32, [c_p, ctypes.POINTER(FdlpPostBatchC), c_i32, c_i32, c_p, ctypes.c_float, c_p]),
+    "fdlp_rnn_set_profiling": (c_i32, [c_p, c_i32]),
+    "fdlp_rnn_times": (c_i32, [c_p, P_dbl]),
     "fdlp_cmvn_norm": (c_i32, [P_dbl, c_i32, c_i32, c_i32, c_i32, P_i32, c_i32, ctypes.POINTER(ctypes.c_float)]),
     "fdlp_noise_params_f64": (c_i32, [P_dbl, c_i64, P_i16, c_i64, c_dbl, c_dbl, P_i64, P_dbl]),
     "fdlp_mat_reader_open": (c_i32, [ctypes.c_char_p, ctypes.POINTER(c_p)]),

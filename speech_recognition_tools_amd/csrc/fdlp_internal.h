@@ -268,6 +268,18 @@ hipError_t launch_dense(const float* A, const float* W, const float* bias, float
                         int relu, hipStream_t s);
 // mode 1: softmax, 2: log_softmax - w prior, in place on x [rows, C]; 0: nothing
 hipError_t launch_row_epilogue(float* x, int64_t rows, int C, int mode, const float* prior, float w, hipStream_t s);
+// The time scan of a GRU layer (gru_scan_kernel, fdlp_nnet.hip): one workgroup per group of up to kGruGU
+// utterances (the M dimension of v_mfma_f32_32x32x2_f32), W_hh streamed in chunks of kGruKC columns.  Slot i of
+// group g is slots[g kGruGU + i]: rows row0 .. row0 + len - 1 of G [rows, 3H] and out [rows, H]; len 0 = empty.
+constexpr int kGruGU = 32, kGruKC = 16;
+struct GruSlot {
+  int64_t row0;
+  int32_t len, pad;
+};
+size_t gru_lds_bytes(int H);     // LDS bytes of a workgroup
+int gru_max_hidden();            // the largest H whose workgroup fits the 160 KB LDS
+hipError_t launch_gru_scan(const float* G, const float* Whh, const float* bhh, float* out, const GruSlot* slots,
+                           int n_groups, int64_t rows, int H, hipStream_t s);
 hipError_t checks_nnet(unsigned int* v, bool reset);
 
 // One utterance of a reverb batch (fdlp_reverb): samples at pcm[off, off+T), y at [yoff, yoff+T+R-1).

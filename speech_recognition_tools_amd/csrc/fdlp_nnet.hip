@@ -284,6 +284,216 @@ hipError_t launch_row_epilogue(float* x, int64_t rows, int C, int mode, const fl
   return hipGetLastError();
 }
 
+// -----------------------------------------------------------------------------------------------------------
+// gru_scan_kernel: the time recurrence of one nn.GRU layer (gate order r, z, n), given the input projection
+// G [rows, 3H] = x W_ih^T + b_ih of every row.  For each utterance, h_{-1} = 0 and for t = 0 .. len - 1
+//     gh = W_hh h_{t-1} + b_hh,  r = s(G_r[t] + gh_r),  z = s(G_z[t] + gh_z),  n = tanh(G_n[t] + r gh_n),
+//     h_t = (1 - z) n + z h_{t-1}            (s the logistic function; h_t is row t of the utterance in out [rows, H])
+//
+// The M dimension of the MFMA is the UTTERANCES: one workgroup of four waves owns a group of up to kGruGU = 32
+// utterances (a GruSlot each; the host sorts by length, fdlp_rnn_plan_groups) and walks t from 0 to the longest
+// length of its group.  No workgroup depends on another.
+//   * h_{t-1} of the group is the A operand, in LDS as [kGruGU][HS] floats, HS = ceil(H / 16) 16 + 4 (the columns
+//     H .. are zero for ever; the row stride is an odd number of 16-byte slots, so a ds_read_b128 lane group falls
+//     on 16 different slots).  Two such buffers: h_t goes to the other one, one barrier per step.
+//   * a wave owns the SAME 32 hidden units j in all three gates, the r, z and n tiles (v_mfma_f32_32x32x2_f32) of
+//     unit block 4 pass + wave, so the gate arithmetic is a register epilogue of its own accumulators.  No other
+//     wave reads its 96 rows of W_hh, so it streams them itself from L2 in chunks of kGruKC = 16 columns through
+//     two LDS buffers of its own ([96][kGruKC + 4] floats): the next chunk's loads are issued before the current
+//     chunk's MFMAs and written to the other buffer after them; LDS operations of one wave complete in order, so
+//     no barrier is needed there.
+//   * every gh element is one chain acc = fmaf(h[k], W_hh[n][k], acc) from acc = +0 over
+//         for g = 0, 8, 16, .. < ceil(H / 16) 16:  for i = 0 .. 3:  k = g + i, then k = g + 4 + i
+//     (a k >= H contributes fmaf(+0, +0, acc): both operands are zero in LDS), and the gates are the explicitly
+//     rounded float32 operations of gru_gate below.  Order and operations depend on H alone, so an utterance's
+//     bits depend on that utterance alone: not on its group, its slot, the other lengths or the batch.
+//   * an utterance with len <= t (or an empty slot, len = 0) still takes part in the MFMA with whatever its row of
+//     the h buffer holds; it loads G from a clamped row, stores nothing, and no other row reads its row.
+// -----------------------------------------------------------------------------------------------------------
+constexpr int kGruThreads = 256;
+constexpr int kGruWS = kGruKC + 4;              // floats between rows of a staged W_hh chunk
+constexpr int kGruWBuf = 3 * 32 * kGruWS;       // floats of one wave's chunk buffer: 96 rows
+constexpr int kGruHead = kGruGU * 3;            // floats of the slot table in LDS: int64 row0[32], int32 len[32]
+static_assert(kGruGU == 32 && kGruKC == 16 && kGruThreads == 256, "the maps of gru_scan_kernel");
+
+static __host__ __device__ int gru_hs(int H) { return (H + kGruKC - 1) / kGruKC * kGruKC + 4; }
+size_t gru_lds_bytes(int H) {
+  return sizeof(float) * ((size_t)kGruHead + 2 * (size_t)kGruGU * gru_hs(H) + (size_t)(kGruThreads / 64) * 2 * kGruWBuf);
+}
+int gru_max_hidden() {
+  int H = kGruKC;
+  while (gru_lds_bytes(H + kGruKC) <= 163840) H += kGruKC;
+  return H;
+}
+
+// One element of the step, every operation rounded to float32 in this order (include/fdlp.h):
+//   a_r = G_r + (acc_r + b_r)     r = 1 / (1 + exp(-a_r))      and z likewise
+//   a_n = G_n + r (acc_n + b_n)   n = tanh(a_n)
+//   h   = (1 - z) n + z h_prev
+__device__ __forceinline__ float gru_sigmoid(float a) { return __fdiv_rn(1.f, __fadd_rn(1.f, expf(-a))); }
+__device__ __forceinline__ float gru_gate(float gr, float gz, float gn, float ar, float az, float an, float br,
+                                          float bz, float bn, float hprev) {
+  const float r = gru_sigmoid(__fadd_rn(gr, __fadd_rn(ar, br)));
+  const float z = gru_sigmoid(__fadd_rn(gz, __fadd_rn(az, bz)));
+  const float n = tanhf(__fadd_rn(gn, __fmul_rn(r, __fadd_rn(an, bn))));
+  return __fadd_rn(__fmul_rn(__fsub_rn(1.f, z), n), __fmul_rn(z, hprev));
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(kGruThreads) void gru_scan_kernel(const float* __restrict__ G,
+                                                               const float* __restrict__ Whh,
+                                                               const float* __restrict__ bhh,
+                                                               float* __restrict__ out,
+                                                               const GruSlot* __restrict__ slots, int64_t rows,
+                                                               int H) {
+  constexpr int NP = 3 * 32 * (kGruKC / 4) / 64;  // 16-byte pieces of a wave's W_hh chunk per lane: 6
+  extern __shared__ float4 gru_sh4[];
+  const int HS = gru_hs(H), HB = kGruGU * HS;
+  int64_t* s_row0 = (int64_t*)gru_sh4;
+  int* s_len = (int*)(s_row0 + kGruGU);
+  float* hb = (float*)gru_sh4 + kGruHead;                      // [2][kGruGU][HS]
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  float* wS = hb + 2 * HB + wave * 2 * kGruWBuf;               // this wave's two chunk buffers
+  const int l31 = lane & 31, hh = lane >> 5;
+  FDLP_CHECK(H >= 1 && rows >= 1 && (!VEC || H % 4 == 0));
+
+  if (tid < kGruGU) {
+    const GruSlot s = slots[(size_t)blockIdx.x * kGruGU + tid];
+    FDLP_CHECK(s.len >= 0 && s.row0 >= 0 && s.row0 + s.len <= rows);
+    s_row0[tid] = s.row0;
+    s_len[tid] = s.len;
+  }
+  for (int i = tid; i < 2 * HB; i += kGruThreads) hb[i] = 0.f;  // h_{-1} = 0, and the columns past H for ever
+  __syncthreads();
+  // the utterances whose results this lane holds: rows (e & 3) + 8 (e >> 2) + 4 hh of every 32 x 32 tile
+  int64_t r0[16];
+  int ln[16];
+  int Tmax = 0;
+#pragma unroll
+  for (int e = 0; e < 16; ++e) {
+    const int u = (e & 3) + 8 * (e >> 2) + 4 * hh;
+    r0[e] = s_row0[u];
+    ln[e] = s_len[u];
+  }
+  for (int u = 0; u < kGruGU; ++u) Tmax = max(Tmax, s_len[u]);
+  Tmax = __builtin_amdgcn_readfirstlane(Tmax);
+
+  const int nub = (H + 31) / 32;       // blocks of 32 hidden units; pass p gives block 4 p + wave to this wave
+  const int kend = HS - 4;
+  const int sq = lane & 3;             // this lane's 16-byte piece of a staged row; its rows are (lane >> 2) + 16 q
+  const int H3 = 3 * H;
+  int cur = 0;
+  for (int t = 0; t < Tmax; ++t, cur ^= 1) {
+    const float* hp = hb + cur * HB;
+    float* hn = hb + (cur ^ 1) * HB;
+    for (int ub = wave; ub < nub; ub += kGruThreads / 64) {
+      const int j = ub * 32 + l31, jc = min(j, H - 1);
+      // this step's G and the biases, from clamped (always valid) addresses: they land during the MFMAs
+      float g[3][16];
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int64_t row = r0[e] + max(min(t, ln[e] - 1), 0);
+        FDLP_CHECK(row >= 0 && row < rows);
+        const float* gp = G + row * H3 + jc;
+        g[0][e] = gp[0];
+        g[1][e] = gp[H];
+        g[2][e] = gp[2 * H];
+      }
+      const float br = bhh[jc], bz = bhh[H + jc], bn = bhh[2 * H + jc];
+      const float* wp[NP];
+#pragma unroll
+      for (int q = 0; q < NP; ++q) {
+        const int r = (lane >> 2) + 16 * q;                     // row of the chunk: gate r >> 5, unit r & 31
+        const int n = (r >> 5) * H + min(ub * 32 + (r & 31), H - 1);
+        FDLP_CHECK(n >= 0 && n < H3);
+        wp[q] = Whh + (size_t)n * H;
+      }
+      nn_f4 pw[NP];
+      auto fetch = [&](int k0) {
+#pragma unroll
+        for (int q = 0; q < NP; ++q) pw[q] = dense_load4<VEC>(wp[q], k0 + 4 * sq, H);
+      };
+      auto stage = [&](float* S, int k0) {
+#pragma unroll
+        for (int q = 0; q < NP; ++q) {
+          const int at = ((lane >> 2) + 16 * q) * kGruWS + 4 * sq;
+          FDLP_CHECK(at >= 0 && at + 3 < kGruWBuf);
+          *(nn_f4*)(S + at) = dense_select4<VEC>(pw[q], k0 + 4 * sq, H, true);
+        }
+      };
+      nn_f16 acc[3];
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[c][e] = 0.f;
+
+      fetch(0);
+      stage(wS, 0);
+      wave_lds_sync();
+      int buf = 0;
+      for (int k0 = 0; k0 < kend; k0 += kGruKC, buf ^= 1) {
+        const float* S = wS + buf * kGruWBuf;
+        const bool more = k0 + kGruKC < kend;
+        if (more) fetch(k0 + kGruKC);
+#pragma unroll
+        for (int gq = 0; gq < kGruKC / 8; ++gq) {
+          const int ka = l31 * HS + k0 + 8 * gq + 4 * hh;
+          FDLP_CHECK(ka >= 0 && ka + 3 < HB);
+          const nn_f4 a = *(const nn_f4*)(hp + ka);
+          nn_f4 w[3];
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {
+            const int kw = (c * 32 + l31) * kGruWS + 8 * gq + 4 * hh;
+            FDLP_CHECK(kw >= 0 && kw + 3 < kGruWBuf);
+            w[c] = *(const nn_f4*)(S + kw);
+          }
+#pragma unroll
+          for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], w[c][i], acc[c], 0, 0, 0);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        if (more) stage(wS + (buf ^ 1) * kGruWBuf, k0 + kGruKC);
+        wave_lds_sync();
+      }
+      if (j < H) {
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+          if (t >= ln[e]) continue;
+          const int u = (e & 3) + 8 * (e >> 2) + 4 * hh;
+          const int at = u * HS + j;
+          FDLP_CHECK(at >= 0 && at < HB && r0[e] + t < rows);
+          const float hv = gru_gate(g[0][e], g[1][e], g[2][e], acc[0][e], acc[1][e], acc[2][e], br, bz, bn, hp[at]);
+          hn[at] = hv;
+          out[(r0[e] + t) * H + j] = hv;
+        }
+      }
+    }
+    __syncthreads();  // h_t is complete, and every read of h_{t-1} is over
+  }
+}
+
+hipError_t launch_gru_scan(const float* G, const float* Whh, const float* bhh, float* out, const GruSlot* slots,
+                           int n_groups, int64_t rows, int H, hipStream_t s) {
+  if (n_groups <= 0 || rows <= 0) return hipSuccess;
+  if (H < 1 || H > gru_max_hidden()) return hipErrorInvalidValue;
+  const bool vec = H % 4 == 0 && ((uintptr_t)Whh & 15u) == 0;
+  const size_t lds = gru_lds_bytes(H);
+#define FDLP_GRU_LAUNCH(VEC)                                                                                     \
+  do {                                                                                                           \
+    if (lds > 65536)                                                                                             \
+      (void)hipFuncSetAttribute((const void*)gru_scan_kernel<VEC>, hipFuncAttributeMaxDynamicSharedMemorySize,   \
+                                (int)lds);                                                                       \
+    hipLaunchKernelGGL((gru_scan_kernel<VEC>), dim3((unsigned)n_groups), dim3(kGruThreads), lds, s, G, Whh, bhh, \
+                       out, slots, rows, H);                                                                     \
+  } while (0)
+  if (vec) FDLP_GRU_LAUNCH(true);
+  else FDLP_GRU_LAUNCH(false);
+#undef FDLP_GRU_LAUNCH
+  return hipGetLastError();
+}
+
 hipError_t checks_nnet(unsigned int* v, bool reset) { return fdlp_checks_local(v, reset); }
 
 }  // namespace fdlp

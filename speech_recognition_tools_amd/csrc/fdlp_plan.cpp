@@ -2200,6 +2200,351 @@ int fdlp_nnet_compute(fdlp_nnet_plan* p, const fdlp_post_batch* b, int32_t tap, 
   return FDLP_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Recurrent plan (cmvn | deltas | splice | GRU stack): a transform plan for stage 0 (a linear stage's [W | b] or a
+// GRU's [W_ih | b_ih]), the other weights on the device, the G buffer of the input projections, two workspaces the
+// stages ping-pong between, and the group table of gru_scan_kernel
+// ---------------------------------------------------------------------------------------------
+struct fdlp_rnn_plan {
+  fdlp_xform_plan* l0 = nullptr;
+  int n_stages = 0, device = -1;
+  std::vector<int> kind, dims;  // n_stages, n_stages + 1
+  int64_t max_rows = 0;
+  int max_utts = 0, max_groups = 0;
+  int max_h = 0;                // widest GRU, 0 without one
+  int widest = 0;               // widest of dims[1 .. n_stages - 1], 0 with one stage
+  float* d_m0 = nullptr;        // [N_0, dims[0] + 1], N_0 = dims[1] or 3 dims[1]
+  std::vector<float*> d_p;      // 4 per stage: w_ih | w, w_hh, b_ih | b, b_hh (stage 0: w_hh and b_hh only)
+  float* d_g = nullptr;
+  float* d_ws[2] = {nullptr, nullptr};
+  fdlp::GruSlot* d_slots = nullptr;
+  fdlp::GruSlot* h_slots = nullptr;  // pinned staging
+  hipEvent_t staging_done = nullptr;
+  bool staging_pending = false;
+  bool profile = false;
+  std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> marks;  // (0 projection | 1 scan, start, stop)
+};
+
+static void rnn_drop_marks(fdlp_rnn_plan* p) {
+  for (auto& m : p->marks) {
+    (void)hipEventDestroy(m.second.first);
+    (void)hipEventDestroy(m.second.second);
+  }
+  p->marks.clear();
+}
+
+static int free_rnn_plan(fdlp_rnn_plan* p) {
+  if (!p) return FDLP_OK;
+  int rc = FDLP_OK;
+  {
+    DeviceGuard dg(p->device);
+    if (p->device >= 0 && p->staging_pending) (void)hipEventSynchronize(p->staging_done);
+    rnn_drop_marks(p);
+    if (p->d_m0) (void)hipFree(p->d_m0);
+    for (float* w : p->d_p)
+      if (w) (void)hipFree(w);
+    if (p->d_g) (void)hipFree(p->d_g);
+    for (float* w : p->d_ws)
+      if (w) (void)hipFree(w);
+    if (p->d_slots) (void)hipFree(p->d_slots);
+    if (p->h_slots) (void)hipHostFree(p->h_slots);
+    if (p->staging_done) (void)hipEventDestroy(p->staging_done);
+    if (p->l0) rc = fdlp_xform_plan_destroy(p->l0);
+  }
+  delete p;
+  return rc;
+}
+
+// Utterances sorted by length, descending and stable, cut into groups of kGruGU: order[i] is the utterance in
+// slot i % kGruGU of group i / kGruGU
+static std::vector<int> rnn_group_order(const int64_t* len, int n) {
+  std::vector<int> order((size_t)n);
+  for (int i = 0; i < n; ++i) order[(size_t)i] = i;
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return len[a] > len[b]; });
+  return order;
+}
+
+int fdlp_rnn_plan_create(const fdlp_rnn_config* cfg, const float* const* params, int64_t max_rows, int32_t max_utts,
+                         fdlp_rnn_plan** out) {
+  if (!cfg || !out) return fail(FDLP_E_INVALID, "fdlp_rnn_plan_create: null argument");
+  *out = nullptr;
+  const int ns = cfg->n_stages;
+  if (ns < 1 || ns > FDLP_RNN_MAX_STAGES)
+    return fail(FDLP_E_INVALID, "the model needs 1 .. " + std::to_string(FDLP_RNN_MAX_STAGES) +
+                                    " stages, got n_stages = " + std::to_string(ns));
+  std::string shape;
+  for (int s = 0; s <= ns; ++s) shape += (s ? " -> " : "") + std::to_string(cfg->dims[s]);
+  for (int s = 0; s < ns; ++s)
+    if (cfg->kind[s] != FDLP_RNN_GRU && cfg->kind[s] != FDLP_RNN_LINEAR && cfg->kind[s] != FDLP_RNN_LINEAR_RELU)
+      return fail(FDLP_E_INVALID, "stage " + std::to_string(s) + " has the unknown kind " +
+                                      std::to_string(cfg->kind[s]) + " (0 GRU, 1 linear, 2 linear with ReLU)");
+  for (int s = 0; s <= ns; ++s)
+    if (cfg->dims[s] < 1)
+      return fail(FDLP_E_INVALID, "model dimension " + std::to_string(s) + " is " + std::to_string(cfg->dims[s]) +
+                                      " (every dimension must be >= 1; dims " + shape + ")");
+  if (max_rows < 1) return fail(FDLP_E_INVALID, "max_rows must be >= 1, got " + std::to_string(max_rows));
+  if (max_utts < 1) return fail(FDLP_E_INVALID, "max_utts must be >= 1, got " + std::to_string(max_utts));
+  int max_h = 0;
+  for (int s = 0; s < ns; ++s)
+    if (cfg->kind[s] == FDLP_RNN_GRU) max_h = std::max(max_h, cfg->dims[s + 1]);
+  if (max_h > fdlp::gru_max_hidden())
+    return fail(FDLP_E_INVALID, "a GRU of " + std::to_string(max_h) + " hidden units needs " +
+                                    std::to_string(fdlp::gru_lds_bytes(max_h)) + " bytes of the 163840-byte LDS; the "
+                                    "widest that fits has " + std::to_string(fdlp::gru_max_hidden()));
+  const bool dev = cfg->post.device >= 0;
+  if (dev && !params) return fail(FDLP_E_INVALID, "fdlp_rnn_plan_create: null params");
+  for (int s = 0; dev && s < ns; ++s) {
+    const bool gru = cfg->kind[s] == FDLP_RNN_GRU;
+    if (!params[4 * s] || !params[4 * s + 2] || (gru && (!params[4 * s + 1] || !params[4 * s + 3])))
+      return fail(FDLP_E_INVALID, "fdlp_rnn_plan_create: null parameters of stage " + std::to_string(s));
+  }
+  auto* p = new (std::nothrow) fdlp_rnn_plan;
+  if (!p) return fail(FDLP_E_NOMEM, "out of memory");
+  p->n_stages = ns;
+  p->device = cfg->post.device;
+  p->kind.assign(cfg->kind, cfg->kind + ns);
+  p->dims.assign(cfg->dims, cfg->dims + ns + 1);
+  p->max_rows = max_rows;
+  p->max_utts = max_utts;
+  p->max_groups = (max_utts + fdlp::kGruGU - 1) / fdlp::kGruGU;
+  p->max_h = max_h;
+  for (int s = 1; s < ns; ++s) p->widest = std::max(p->widest, cfg->dims[s]);
+  p->d_p.assign((size_t)ns * 4, nullptr);
+  int rc;
+#define RNN_FAIL(code, msg) do { rc = fail(code, msg); free_rnn_plan(p); return rc; } while (0)
+#define RNN_TRY(expr)                            \
+  do {                                           \
+    rc = (expr);                                 \
+    if (rc != FDLP_OK) {                         \
+      std::string m_ = fdlp::last_error_slot();  \
+      free_rnn_plan(p);                          \
+      fdlp::last_error_slot() = m_;              \
+      return rc;                                 \
+    }                                            \
+  } while (0)
+  const int N0 = cfg->kind[0] == FDLP_RNN_GRU ? 3 * cfg->dims[1] : cfg->dims[1];
+  fdlp_xform_config xc{};
+  xc.post = cfg->post;
+  xc.out_dim = N0;
+  xc.affine = 1;
+  RNN_TRY(fdlp_xform_plan_create(&xc, &p->l0));
+  const int K0 = p->l0->post->Dout;
+  if (K0 != cfg->dims[0])
+    RNN_FAIL(FDLP_E_INVALID, "the model's input dimension dims[0] = " + std::to_string(cfg->dims[0]) +
+                                 " differs from the " + std::to_string(K0) + " columns the stages before it give");
+  if (!dev) {
+    *out = p;
+    return FDLP_OK;
+  }
+  DeviceGuard dg(p->device);
+  if (dg.status() != hipSuccess) RNN_FAIL(FDLP_E_HIP, "hipSetDevice failed");
+  {
+    // stage 0's input side as transform-feats' affine matrix: [W | b]
+    std::vector<float> m0((size_t)N0 * (K0 + 1));
+    for (int n = 0; n < N0; ++n) {
+      memcpy(&m0[(size_t)n * (K0 + 1)], params[0] + (size_t)n * K0, sizeof(float) * K0);
+      m0[(size_t)n * (K0 + 1) + K0] = params[2][n];
+    }
+    RNN_TRY(upload(&p->d_m0, m0.data(), m0.size()));
+  }
+  for (int s = 0; s < ns; ++s) {
+    const int K = cfg->dims[s], N = cfg->dims[s + 1];
+    const bool gru = cfg->kind[s] == FDLP_RNN_GRU;
+    if (s > 0) {
+      RNN_TRY(upload(&p->d_p[4 * (size_t)s], params[4 * s], (size_t)(gru ? 3 * N : N) * K));
+      RNN_TRY(upload(&p->d_p[4 * (size_t)s + 2], params[4 * s + 2], (size_t)(gru ? 3 * N : N)));
+    }
+    if (gru) {
+      RNN_TRY(upload(&p->d_p[4 * (size_t)s + 1], params[4 * s + 1], (size_t)3 * N * N));
+      RNN_TRY(upload(&p->d_p[4 * (size_t)s + 3], params[4 * s + 3], (size_t)3 * N));
+    }
+  }
+  auto zeroed = [&](float** w, size_t n, const char* what) -> int {
+    if (n == 0) return FDLP_OK;
+    if (hipMalloc((void**)w, sizeof(float) * n) != hipSuccess) {
+      *w = nullptr;
+      return fail(FDLP_E_NOMEM, std::string("recurrent plan: allocation of ") + what + " failed: " +
+                                    std::to_string(n) + " float32 for " + std::to_string(max_rows) + " rows");
+    }
+    // rows no utterance covers are read by the dense launches (and never stored into an utterance's rows)
+    if (hipMemset(*w, 0, sizeof(float) * n) != hipSuccess) return fail(FDLP_E_HIP, "recurrent plan: memset failed");
+    return FDLP_OK;
+  };
+  RNN_TRY(zeroed(&p->d_g, (size_t)max_rows * 3 * p->max_h, "the projection buffer"));
+  for (float*& w : p->d_ws) RNN_TRY(zeroed(&w, (size_t)max_rows * p->widest, "a stage workspace"));
+  const size_t nslots = (size_t)p->max_groups * fdlp::kGruGU;
+  if (hipMalloc((void**)&p->d_slots, sizeof(fdlp::GruSlot) * nslots) != hipSuccess ||
+      hipHostMalloc((void**)&p->h_slots, sizeof(fdlp::GruSlot) * nslots, hipHostMallocDefault) != hipSuccess)
+    RNN_FAIL(FDLP_E_NOMEM, "recurrent plan: group table allocation failed");
+  if (hipEventCreateWithFlags(&p->staging_done, hipEventDisableTiming) != hipSuccess)
+    RNN_FAIL(FDLP_E_NOMEM, "recurrent plan: event creation failed");
+#undef RNN_TRY
+#undef RNN_FAIL
+  *out = p;
+  return FDLP_OK;
+}
+
+int fdlp_rnn_plan_destroy(fdlp_rnn_plan* p) { return free_rnn_plan(p); }
+
+int fdlp_rnn_plan_info(const fdlp_rnn_plan* p, int32_t* in_dim, int32_t* n_stages, int32_t* out_dims,
+                       int64_t* workspace_bytes, int32_t* group_utts, int32_t* lds_bytes) {
+  if (!p) return fail(FDLP_E_INVALID, "fdlp_rnn_plan_info: null plan");
+  if (in_dim) *in_dim = p->dims[0];
+  if (n_stages) *n_stages = p->n_stages;
+  if (out_dims)
+    for (int s = 0; s < p->n_stages; ++s) out_dims[s] = p->dims[(size_t)s + 1];
+  if (workspace_bytes)
+    *workspace_bytes = (int64_t)sizeof(float) * p->max_rows * (3 * (int64_t)p->max_h + 2 * (int64_t)p->widest) +
+                       (int64_t)sizeof(fdlp::GruSlot) * p->max_groups * fdlp::kGruGU;
+  if (group_utts) *group_utts = fdlp::kGruGU;
+  if (lds_bytes) *lds_bytes = p->max_h ? (int32_t)fdlp::gru_lds_bytes(p->max_h) : 0;
+  return FDLP_OK;
+}
+
+int fdlp_rnn_plan_groups(const fdlp_rnn_plan* p, const int32_t* lengths, int32_t n_utts, int32_t* group_of,
+                         int32_t* slot_of, int32_t* n_groups) {
+  if (!p || n_utts < 0 || (n_utts > 0 && !lengths)) return fail(FDLP_E_INVALID, "fdlp_rnn_plan_groups: bad arguments");
+  std::vector<int64_t> len((size_t)n_utts);
+  for (int u = 0; u < n_utts; ++u) {
+    if (lengths[u] < 1)
+      return fail(FDLP_E_INVALID, "utterance " + std::to_string(u) + " has length " + std::to_string(lengths[u]) +
+                                      " (every length must be >= 1)");
+    len[(size_t)u] = lengths[u];
+  }
+  const std::vector<int> order = rnn_group_order(len.data(), n_utts);
+  for (int i = 0; i < n_utts; ++i) {
+    if (group_of) group_of[order[(size_t)i]] = i / fdlp::kGruGU;
+    if (slot_of) slot_of[order[(size_t)i]] = i % fdlp::kGruGU;
+  }
+  if (n_groups) *n_groups = (n_utts + fdlp::kGruGU - 1) / fdlp::kGruGU;
+  return FDLP_OK;
+}
+
+int fdlp_rnn_set_profiling(fdlp_rnn_plan* p, int32_t on) {
+  if (!p) return fail(FDLP_E_INVALID, "fdlp_rnn_set_profiling: null plan");
+  p->profile = on != 0;
+  return FDLP_OK;
+}
+
+int fdlp_rnn_times(fdlp_rnn_plan* p, double* ms) {
+  if (!p || !ms) return fail(FDLP_E_INVALID, "fdlp_rnn_times: null argument");
+  ms[0] = ms[1] = 0.0;
+  DeviceGuard dg(p->device);
+  for (auto& m : p->marks) {
+    float t = 0.f;
+    HIP_TRY(hipEventSynchronize(m.second.second));
+    HIP_TRY(hipEventElapsedTime(&t, m.second.first, m.second.second));
+    ms[m.first] += t;
+  }
+  rnn_drop_marks(p);
+  return FDLP_OK;
+}
+
+int fdlp_rnn_compute(fdlp_rnn_plan* p, const fdlp_post_batch* b, int32_t tap, int32_t mode, const void* prior_dev,
+                     float prior_weight, void* stream) {
+  if (!p || !b) return fail(FDLP_E_INVALID, "fdlp_rnn_compute: null argument");
+  if (p->device < 0) return fail(FDLP_E_INVALID, "fdlp_rnn_compute: host-only plan");
+  if (tap < 0 || tap >= p->n_stages)
+    return fail(FDLP_E_INVALID, "tap " + std::to_string(tap) + " is outside 0 .. " + std::to_string(p->n_stages - 1) +
+                                    " (the model has " + std::to_string(p->n_stages) + " stages)");
+  if (mode != FDLP_NNET_RAW && mode != FDLP_NNET_SOFTMAX && mode != FDLP_NNET_LOGLIKE)
+    return fail(FDLP_E_INVALID, "fdlp_rnn_compute: unknown mode " + std::to_string(mode));
+  if (mode != FDLP_NNET_RAW && tap != 0)
+    return fail(FDLP_E_INVALID, "softmax and loglike apply to the last stage only (tap 0), got tap " +
+                                    std::to_string(tap));
+  if (mode == FDLP_NNET_LOGLIKE && (!prior_dev || ((uintptr_t)prior_dev & 3u)))
+    return fail(FDLP_E_INVALID, "loglike needs a 4-byte aligned device prior vector");
+  if (b->n_utt > p->max_utts)
+    return fail(FDLP_E_INVALID, "batch of " + std::to_string(b->n_utt) + " utterances exceeds the plan's max_utts " +
+                                    std::to_string(p->max_utts));
+  if (b->n_rows > p->max_rows)
+    return fail(FDLP_E_CAPACITY, "batch of " + std::to_string(b->n_rows) + " rows exceeds the plan's max_rows " +
+                                     std::to_string(p->max_rows));
+  if (b->n_utt > 0 && (!b->out_dev || ((uintptr_t)b->out_dev & 3u) || !b->row_off || !b->utt_len))
+    return fail(FDLP_E_INVALID, "fdlp_rnn_compute: bad batch (out_dev must be a 4-byte aligned device pointer)");
+  // the scans index G and the stage outputs through the group table: every utterance inside the batch's rows
+  for (int u = 0; u < b->n_utt; ++u) {
+    const int64_t T = b->utt_len[u], r0 = b->row_off[u];
+    if (T < 1 || T > p->max_rows || T > INT32_MAX || r0 < 0 || r0 > b->n_rows - T)
+      return fail(FDLP_E_INVALID, "utterance " + std::to_string(u) + " has length " + std::to_string(T) +
+                                      " at row " + std::to_string(r0) + " of a batch of " +
+                                      std::to_string(b->n_rows) + " rows (every length must be >= 1 and inside it)");
+  }
+  const int last = p->n_stages - 1 - tap;  // the tapped stage
+  hipStream_t s = (hipStream_t)stream;
+  auto gru = [&](int st) { return p->kind[(size_t)st] == FDLP_RNN_GRU; };
+  // where stage st's output goes, and where its input comes from
+  auto dst = [&](int st) { return st == last ? (float*)b->out_dev : p->d_ws[st & 1]; };
+  DeviceGuard dg(p->device);
+  HIP_TRY(dg.status());
+  hipEvent_t ev0 = nullptr;
+  auto mark_begin = [&]() -> hipError_t {
+    if (!p->profile) return hipSuccess;
+    hipError_t e = hipEventCreate(&ev0);
+    return e != hipSuccess ? e : hipEventRecord(ev0, s);
+  };
+  auto mark_end = [&](int cls) -> hipError_t {
+    if (!p->profile) return hipSuccess;
+    hipEvent_t ev1 = nullptr;
+    hipError_t e = hipEventCreate(&ev1);
+    if (e == hipSuccess) e = hipEventRecord(ev1, s);
+    p->marks.push_back({cls, {ev0, ev1}});
+    return e;
+  };
+  // stage 0's input side in the chain's launch; its batch checks are the chain's
+  fdlp_post_batch b0 = *b;
+  b0.out_dev = gru(0) ? p->d_g : dst(0);
+  fdlp::XformConsts xc{};
+  xc.N = gru(0) ? 3 * p->dims[1] : p->dims[1]; xc.C = p->dims[0] + 1; xc.affine = 1; xc.n_mat = 1;
+  HIP_TRY(mark_begin());
+  {
+    const int rc = post_compute(p->l0->post, &b0, stream, &xc, p->d_m0, nullptr);
+    if (rc != FDLP_OK) return rc;
+  }
+  HIP_TRY(mark_end(0));
+  if (b->n_utt == 0 || b->n_rows == 0) return FDLP_OK;
+  // the group table, once per batch
+  const int ng = (b->n_utt + fdlp::kGruGU - 1) / fdlp::kGruGU;
+  if (p->max_h > 0) {
+    if (p->staging_pending) {
+      HIP_TRY(hipEventSynchronize(p->staging_done));
+      p->staging_pending = false;
+    }
+    const std::vector<int> order = rnn_group_order(b->utt_len, b->n_utt);
+    for (int i = 0; i < ng * fdlp::kGruGU; ++i) {
+      fdlp::GruSlot& sl = p->h_slots[i];
+      sl.row0 = i < b->n_utt ? b->row_off[order[(size_t)i]] : 0;
+      sl.len = i < b->n_utt ? (int32_t)b->utt_len[order[(size_t)i]] : 0;
+      sl.pad = 0;
+    }
+    HIP_TRY(hipMemcpyAsync(p->d_slots, p->h_slots, sizeof(fdlp::GruSlot) * ng * fdlp::kGruGU, hipMemcpyHostToDevice,
+                           s));
+    HIP_TRY(hipEventRecord(p->staging_done, s));
+    p->staging_pending = true;
+  }
+  for (int st = 0; st <= last; ++st) {
+    const int K = p->dims[(size_t)st], N = p->dims[(size_t)st + 1];
+    const float* const* w = &p->d_p[4 * (size_t)st];
+    if (st > 0) {
+      const float* in = p->d_ws[(st - 1) & 1];
+      const int relu = p->kind[(size_t)st - 1] == FDLP_RNN_LINEAR_RELU;
+      HIP_TRY(mark_begin());
+      HIP_TRY(fdlp::launch_dense(in, w[0], w[2], gru(st) ? p->d_g : dst(st), b->n_rows, K, gru(st) ? 3 * N : N, relu,
+                                 s));
+      HIP_TRY(mark_end(0));
+    }
+    if (gru(st)) {
+      HIP_TRY(mark_begin());
+      HIP_TRY(fdlp::launch_gru_scan(p->d_g, w[1], w[3], dst(st), p->d_slots, ng, b->n_rows, N, s));
+      HIP_TRY(mark_end(1));
+    }
+  }
+  if (mode != FDLP_NNET_RAW)
+    HIP_TRY(fdlp::launch_row_epilogue((float*)b->out_dev, b->n_rows, p->dims[(size_t)p->n_stages], mode,
+                                      (const float*)prior_dev, prior_weight, s));
+  return FDLP_OK;
+}
+
 int fdlp_reverb(const fdlp_reverb_batch* b, void* stream) {
   if (!b || b->n_utt < 0 || !b->pcm_off || !b->utt_len || !b->rir_dev || b->rir_len < 1 || !b->out_dev ||
       !b->out_len || (b->n_utt > 0 && !b->pcm_dev) || (b->noise_dev && (!b->noise_off || !b->noise_alpha)) ||

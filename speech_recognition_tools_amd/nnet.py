@@ -21,7 +21,7 @@ time on the CPU.
     reference raises a NameError there, extract_posterior.py:42-51; the data-prep script plainly means raw).
   * The ark values are rounded like dict2Ark's '%.3f' text ark read back by copy-feats, by the rule include/fdlp.h
     documents for ark_decimals: k = nearbyint(v * 10^d), stored as (float)(k / 10^d).
-Out of scope: everything recurrent in src/nnet, and training.
+Out of scope: training.  The GRU models of src/nnet (dump_genclassifier_outputs.py) are in rnn.py.
 """
 import argparse
 import ctypes
@@ -349,6 +349,13 @@ class NnetRunner:
             self.num_done += 1
         sl.keys, sl.lens, sl.fill, sl.done = [], [], 0, None
 
+    def _admit(self, utt):
+        """hook: False skips the utterance (the hook has logged and counted it); anything else goes to _added"""
+        return None
+
+    def _added(self, sl, extra):
+        """hook: the utterance _admit returned `extra` for has been appended to slot sl"""
+
     def run(self, rspecifier: str, writer: FeatWriter):
         cur = 0
         for utt, m in MatReader(rspecifier):
@@ -357,6 +364,9 @@ class NnetRunner:
             if m.shape[0] == 0 or m.shape[1] != self.dim:
                 self.log("Empty or mismatched feature matrix for utterance %s (%d x %d)" % (utt, m.shape[0], m.shape[1]))
                 self.num_err += 1
+                continue
+            extra = self._admit(utt)
+            if extra is False:
                 continue
             sl = self.slots[cur]
             if sl.fill and sl.fill + m.shape[0] > sl.rows:
@@ -373,6 +383,7 @@ class NnetRunner:
             sl.fill += m.shape[0]
             sl.keys.append(utt)
             sl.lens.append(m.shape[0])
+            self._added(sl, extra)
         if self.slots:
             if self.slots[cur].fill:
                 self._launch(self.slots[cur])
