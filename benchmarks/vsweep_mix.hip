@@ -5,10 +5,14 @@
 //   lds   : dpp + the window's A new values and cur read from an LDS ring each block (two banks)
 //   ldsdpp / ldsrev / ldsrev0 / ldsrevc : the kernel's own block (v_fmac_f64_dpp broadcasts,
 //           window reads at the block head) in two FMA orders, see krev below
+//   kx modes (argument "ctl"): ldsrev plus the kernel's per-block control flow, see kx below
 // The ring rows are 544 doubles, the kernel's conflict-free stride.
 // Build: hipcc -O3 --offload-arch=gfx950 benchmarks/vsweep_mix.hip -o benchmarks/vsweep_mix
 #include <hip/hip_runtime.h>
+#include <limits.h>
 #include <stdio.h>
+#include <string.h>
+#include <type_traits>
 
 constexpr int A = 10;
 template <int K>
@@ -206,6 +210,117 @@ __global__ __launch_bounds__(64, 2) void krev(const double* in, double* out, int
   out[blockIdx.x * 64 + threadIdx.x] = s;
 }
 
+// kx: ldsrev (krev<1, true, true>) plus the per-block control flow that ac_vsweep_kernel's block carries and
+// the microbenchmark's does not, one piece at a time.  Every test is wave-uniform and never true at run time
+// (its operands are kernel arguments and table words, so the compiler keeps it); what is priced is the
+// compare, the branch, and what their presence does to the waits and the schedule around them.
+//   X_BR1  if (n >= ev) { handler }  ahead of the block: the kernel's `while (evS >= hi_m)`; the handler
+//          stores an accumulator row and takes the next record
+//   X_BR2  also if (n >= lim) { handler }: the kernel's ensure(); the handler writes the ring, as commit does
+//   X_SEL  cur = (pos >= lo_m && pos < hi_m) ? cur : 0 with lo_m, hi_m as the kernel builds them
+//   X_SLD  a four-word record requested by a scalar load in every block and taken in (asm "s" use) at the
+//          head of the next, ahead of its ring reads, as the kernel takes nx in
+//   X_ALL  BR1 + BR2 + SEL with the record requested in BR1's handler only and taken in at every block head:
+//          the kernel's shape (the wait at the head is then the compiler's, for a load that may be pending)
+//   R > 0  schedule walk: an outer loop does X_ALL's tests and takes one record in (requested one record
+//          ahead); the record's second word is the count of (X, Y) block pairs that the inner loop then runs
+//          with nothing but the blocks.  iters is still the total number of pairs.
+typedef int Rec4 __attribute__((ext_vector_type(4), aligned(4)));
+constexpr int X_BR1 = 1, X_BR2 = 2, X_SEL = 4, X_SLD = 8, X_ALL = 16;
+template <int X, int R>
+__global__ __launch_bounds__(64, 2) void kx(const double* in, double* out, int iters, const Rec4* __restrict__ tab,
+                                            int ev, int lim, int nlo, int nhi) {
+  __shared__ double ring[4][544];
+  const int l = threadIdx.x & 15, row = threadIdx.x >> 4;
+  for (int q = l; q < 544; q += 16) ring[row][q] = in[(q + row) & 255] + 1e-3 * q;
+  __syncthreads();
+  double acc[A], Xb[A], Yb[A];
+  for (int u = 0; u < A; ++u) { acc[u] = 0; Xb[u] = in[u + l]; Yb[u] = in[u + 20 + l]; }
+  double cur = ring[row][l];
+  constexpr bool br1 = (X & (X_BR1 | X_ALL)) != 0, br2 = (X & (X_BR2 | X_ALL)) != 0, sel = (X & (X_SEL | X_ALL)) != 0;
+  constexpr bool takein = (X & (X_SLD | X_ALL)) != 0 || R > 0;
+  int k = 0;
+  Rec4 nx = tab[0];
+  auto request = [&]() { ++k; nx = tab[__builtin_amdgcn_readfirstlane(k & 63)]; };
+  auto checks = [&](int n) {
+    if constexpr (br1) {
+      if (n >= ev) {  // never
+        out[blockIdx.x * 64 + threadIdx.x] = acc[0];
+        ev = nx.x;
+        request();
+      }
+    }
+    if constexpr (br2) {
+      if (n >= lim) {  // never
+        lim += 256;
+        ring[row][(n + l) & 511] = in[n & 4095];
+      }
+    }
+  };
+  // FULL: the block with its extras; otherwise the bare ldsrev block
+  auto blk = [&](auto full, int n, double (&lo)[A], const double (&hi)[A]) {
+    constexpr bool FULL = decltype(full)::value;
+    const int n0 = n & 511;
+    if constexpr (FULL) checks(n);
+    if constexpr (FULL && takein) asm volatile("" ::"s"(nx));
+    const int base = (n0 + A * l) & 510;
+#pragma unroll
+    for (int q = 0; q < A; ++q) lo[q] = ring[row][base + q];
+    double c = cur;
+    cur = ring[row][(n0 + A + l) & 511];
+    if constexpr (FULL && (X & X_SLD) != 0) request();
+    if constexpr (FULL && sel) {
+      const int pos = n + l, hi_m = min(n + A, nhi), lo_m = max(max(ev, n), nlo);
+      c = (pos >= lo_m && pos < hi_m) ? c : 0.0;
+    }
+    double cm;
+    asm volatile("v_mov_b64 %0, %1\n\ts_nop 1" : "=v"(cm) : "v"(c));
+    fma_seq<1, true>(acc, cm, lo, hi);
+  };
+  if constexpr (R == 0) {
+    for (int it = 0; it < iters; ++it) {
+      blk(std::true_type{}, it * 2 * A, Xb, Yb);
+      blk(std::true_type{}, it * 2 * A + A, Yb, Xb);
+    }
+  } else {
+    for (int it = 0; it < iters;) {
+      checks(it * 2 * A);
+      asm volatile("" ::"s"(nx));
+      const int run = nx.y;  // = R
+      request();
+#pragma unroll 1
+      for (int e = it + run; it < e; ++it) {
+        blk(std::false_type{}, it * 2 * A, Xb, Yb);
+        blk(std::false_type{}, it * 2 * A + A, Yb, Xb);
+      }
+    }
+  }
+  double s = 0;
+  for (int u = 0; u < A; ++u) s += acc[u];
+  out[blockIdx.x * 64 + threadIdx.x] = s;
+}
+
+template <int X, int R>
+static void runx(const char* name, const double* in, double* out, Rec4* tab, int waves, int iters) {
+  int h[64][4];
+  for (auto& r : h) { r[0] = INT_MAX; r[1] = R; r[2] = r[3] = 0; }
+  hipMemcpy(tab, h, sizeof(h), hipMemcpyHostToDevice);
+  hipEvent_t a, b;
+  hipEventCreate(&a); hipEventCreate(&b);
+  auto go = [&](int n) {
+    hipLaunchKernelGGL((kx<X, R>), dim3(waves), dim3(64), 0, 0, in, out, n, tab, INT_MAX, INT_MAX, INT_MIN, INT_MAX);
+  };
+  go(16);
+  hipEventRecord(a);
+  go(iters);
+  hipEventRecord(b);
+  hipEventSynchronize(b);
+  float ms = 0;
+  hipEventElapsedTime(&ms, a, b);
+  const double flops = 2.0 * 2 * A * A * 64.0 * waves * (double)iters;
+  printf("%-8s waves %5d  %.3f ms  %.1f TFLOP/s\n", name, waves, ms, flops / ms / 1e9);
+}
+
 template <int MODE>
 static void launch(dim3 g, const double* in, double* out, int iters) {
   if constexpr (MODE == 5) hipLaunchKernelGGL((krev<0, false, false>), g, dim3(64), 0, 0, in, out, iters);
@@ -231,13 +346,36 @@ static void run(const char* name, const double* in, double* out, int waves, int 
   printf("%-8s waves %5d  %.3f ms  %.1f TFLOP/s\n", name, waves, ms, flops / ms / 1e9);
 }
 
-int main() {
+// vsweep_mix       : the instruction mixes
+// vsweep_mix ctl   : ldsrev against the kx modes (the kernel's per-block control flow), twice over so that
+//                    the run-to-run spread stands next to the differences
+int main(int argc, char** argv) {
   double *in, *out;
   hipMalloc(&in, 4096 * sizeof(double));
   hipMalloc(&out, 65536 * 64 * sizeof(double));
   double h[4096];
   for (int i = 0; i < 4096; ++i) h[i] = 1.0 + 1e-6 * i;
   hipMemcpy(in, h, sizeof(h), hipMemcpyHostToDevice);
+  if (argc > 1 && !strcmp(argv[1], "ctl")) {
+    Rec4* tab;
+    hipMalloc(&tab, 64 * sizeof(Rec4));
+    for (int rep = 0; rep < 2; ++rep)
+      for (int waves : {1024, 2048}) {
+        run<6>("ldsrev", in, out, waves, 20000);
+        runx<0, 0>("kx", in, out, tab, waves, 20000);
+        runx<X_BR1, 0>("br1", in, out, tab, waves, 20000);
+        runx<X_BR1 | X_BR2, 0>("br2", in, out, tab, waves, 20000);
+        runx<X_SEL, 0>("sel", in, out, tab, waves, 20000);
+        runx<X_SLD, 0>("sld", in, out, tab, waves, 20000);
+        runx<X_ALL, 0>("all", in, out, tab, waves, 20000);
+        runx<X_ALL, 1>("run1", in, out, tab, waves, 20000);
+        runx<X_ALL, 2>("run2", in, out, tab, waves, 20000);
+        runx<X_ALL, 4>("run4", in, out, tab, waves, 20000);
+        runx<X_ALL, 8>("run8", in, out, tab, waves, 20000);
+        runx<X_ALL, 16>("run16", in, out, tab, waves, 20000);
+      }
+    return 0;
+  }
   for (int waves : {1024, 2048, 4096, 8192}) {
     run<0>("fma", in, out, waves, 20000);
     run<1>("dpp", in, out, waves, 20000);

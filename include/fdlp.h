@@ -223,6 +223,15 @@ int fdlp_plan_regions(const fdlp_plan* plan, int32_t* m1, int32_t* m2);
  * 0 restart / 1 emit, chain) in sweep order; *nev receives the event count. */
 int fdlp_plan_flat_events(const fdlp_plan* plan, int32_t* chains, int32_t* parts, int32_t* nev, int32_t* events,
                           int32_t cap);
+/* The walk of one lag-parallel VALU sweep over its positions, as ac_vsweep_kernel takes it (DESIGN.md
+ * "Lag-parallel VALU sweeps"): kind 0 lower skirt, 1 upper skirt, 2 flat tops (part < parts of
+ * fdlp_plan_flat_events).  Up to cap records (run, action, pos, aux) in sweep order, top-down: `run` whole
+ * blocks taken without a test (always even), then action 0 = commit the staged chunk that starts at pos,
+ * 1 = one general block at base pos handling aux events, 2 = end of the sweep with aux events left.
+ * info[4] = lags per lane A (the block length), positions per chunk, sweep limits nlo, nhi.  Computed on the
+ * host from the plan alone (host-only plans too); *nrec = 0 when the plan has no VALU sweeps. */
+int fdlp_plan_sweep_schedule(const fdlp_plan* plan, int32_t kind, int32_t part, int32_t* info, int32_t* nrec,
+                             int32_t* recs, int32_t cap);
 /* fdlp_compute splits a batch of F frames into min(n_sub, F/256) sub-batches that alternate
  * between the caller's stream and a second stream of the plan, so the MFMA-bound autocorrelation
  * of one sub-batch can overlap the VALU-bound kernels of the other (default 1 = serial: on MI355X

@@ -178,6 +178,7 @@ SIGNATURES = {
     "fdlp_autocorr_path": (c_i32, [c_p]),
     "fdlp_plan_regions": (c_i32, [c_p, c_p, c_p]),
     "fdlp_plan_flat_events": (c_i32, [c_p, c_p, c_p, c_p, c_p, c_i32]),
+    "fdlp_plan_sweep_schedule": (c_i32, [c_p, c_i32, c_i32, c_p, c_p, c_p, c_i32]),
     "fdlp_set_lpc_path": (c_i32, [c_p, c_i32]),
     "fdlp_plan_lpc_dispatch": (c_i32, [c_p, P_i32]),
     "fdlp_device_checks": (c_i32, [c_p, c_p, c_p, c_i32]),

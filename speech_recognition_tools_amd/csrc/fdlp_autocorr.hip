@@ -682,14 +682,14 @@ constexpr int kVsMirror = 16;
 // 10-double lane stride of the window reads.  (Skirt sweeps at three waves per SIMD -- a 320-position
 // ring, 128-position chunks, one parked row -- measured 1.56 -> 2.19 ms, r03s: not kept.)
 template <int C>
-constexpr int vs_ring() { return 512; }
+constexpr int vs_ring() { return kVsRingPositions; }
 template <int C>
 constexpr int vs_row() { return 544; }
 // positions staged per chunk; the prefetch of the next chunk has to cover the HBM latency under load
 // (64 positions, ~3000 cycles of FMAs, measured too short).  The flat sweep keeps its chains in
 // registers, so it stages 128 at a time to stay at two waves per SIMD.
 template <int A, int C>
-constexpr int vs_chunk() { return (C == 0 && 18 * A < vs_ring<C>() - 256) ? 256 : 128; }
+constexpr int vs_chunk() { return vs_chunk_positions(A, C > 0); }
 template <int C>
 constexpr int vs_waves_per_simd() { return 2; }
 
@@ -1067,7 +1067,31 @@ __global__ __launch_bounds__(64, vs_waves_per_simd<C>()) void ac_vsweep_kernel(D
 #pragma unroll
     for (int q = 0; q < A; ++q) Y[q] = rg[base + q];
   }
+  // A whole block with nothing to decide: no event at or above its base, no sweep end inside it, and the block
+  // below it already staged.  Then block() would run one unmasked pass (the select only zeroes lanes >= A, which
+  // no broadcast reads), so the same FMAs in the same order without the tests.
+  auto plain = [&](int n0, double (&lo)[A], const double (&hi)[A]) __attribute__((always_inline)) {
+    FDLP_CHECK(evS < n0 && n0 >= nlo && n0 + A <= nhi && n0 - A >= A * b_bot);
+    FDLP_CHECK(n0 - A >= lo_loaded && n0 + 16 * A <= lo_loaded + kVsRing);
+    const int base = slot_add(n0, A * l);
+#pragma unroll
+    for (int q = 0; q < A; ++q) lo[q] = rg[base + q];
+    const double cur = cur_ahead;
+    cur_ahead = rg[slot_add(n0 - A, l)];
+    vs_fma_block<A>(acc, cur, lo, hi);
+  };
+  const int b_whole = vs_whole_top(nhi, A);
   for (int b = b_top; b >= b_bot;) {
+    // The run's length depends only on the plan (events, sweep limits, chunk grid), never on the frame, and is
+    // worked out here in scalar registers from state the wave holds anyway (vs_run_pairs: three divisions by A,
+    // ahead of every general pair, also where it comes to 0); fdlp_plan_sweep_schedule replays the walk on
+    // the host with the same functions.
+#pragma unroll 1
+    for (int m = vs_run_pairs(b, b_whole, evS, lo_loaded, b_bot, A); m > 0; --m) {  // (X, Y) pairs: the bank parity is kept
+      plain(A * b, X, Y);
+      plain(A * b - A, Y, X);
+      b -= 2;
+    }
     block(A * b, X, Y);
     if (--b < b_bot) break;
     block(A * b, Y, X);

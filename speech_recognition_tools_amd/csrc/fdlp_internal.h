@@ -58,6 +58,37 @@ struct FlatEv {
   int32_t S, band, type, chain;
 };
 
+// ac_vsweep_kernel's sweep geometry and block schedule, shared with the host's replay of it
+// (fdlp_plan_sweep_schedule): ring positions per unit, positions staged per chunk, and the rule for the
+// runs of whole blocks that the kernel takes without a test.
+constexpr int kVsRingPositions = 512;
+constexpr int vs_chunk_positions(int A, bool flat) { return (!flat && 18 * A < kVsRingPositions - 256) ? 256 : 128; }
+// The lowest block (index = base / A) that is still "plain" when the next event is at evS (-1: none), the
+// staged positions start at lo_loaded and the sweep's last block is b_bot: its base lies above the event, the
+// block below it is staged, and it is not the last block.  Blocks from there up to the current one (if that
+// ends at or below the sweep's top) hold no event, no sweep end and need no chunk: one unmasked pass each.
+__host__ __device__ inline int vs_plain_low(int evS, int lo_loaded, int b_bot, int A) {
+  const int be = (evS + A) / A, bs = (lo_loaded + A - 1) / A + 1, bb = b_bot + 1;
+  const int m = be > bs ? be : bs;
+  return m > bb ? m : bb;
+}
+// The highest block that ends at or below the sweep's top nhi (the top block itself may be cut by nhi).
+__host__ __device__ inline int vs_whole_top(int nhi, int A) { return nhi / A - 1; }
+// Number of (X, Y) pairs of plain blocks to run from block b down before the next general block; 0 when b is
+// above b_whole or fewer than two plain blocks are left (b - low + 1 is then below 2, possibly negative).
+__host__ __device__ inline int vs_run_pairs(int b, int b_whole, int evS, int lo_loaded, int b_bot, int A) {
+  if (b > b_whole) return 0;
+  const int n = b - vs_plain_low(evS, lo_loaded, b_bot, A) + 1;
+  return n > 0 ? n >> 1 : 0;
+}
+// One step of a sweep's schedule as the host lists it: `run` plain blocks (always even: (X, Y) bank
+// pairs), then the action -- commit the chunk that starts at pos, run the general block at base pos
+// (aux = events it handles), or end the sweep (aux = events handled after the last block).
+enum VsAction { kVsCommit = 0, kVsGeneral = 1, kVsEnd = 2 };
+struct VsRec {
+  int32_t run, action, pos, aux;
+};
+
 // Device-resident constants of a plan.
 struct DevConsts {
   int B, N, hop, ext, p, nlags, M, Me, kk, env_nfft;

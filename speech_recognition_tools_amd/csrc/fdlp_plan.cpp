@@ -1175,6 +1175,80 @@ int fdlp_plan_flat_events(const fdlp_plan* p, int32_t* chains, int32_t* parts, i
   return FDLP_OK;
 }
 
+// ac_vsweep_kernel's walk over one sweep, replayed on the host: the same limits, chunk grid, event order and
+// run rule (vs_plain_low) as the kernel, none of the data.
+static std::vector<fdlp::VsRec> sweep_schedule(const fdlp_plan* p, int kind, int part, int32_t* info) {
+  const SkirtTables& T = p->sk;
+  const int A = fdlp::vsweep_lanes_lags(p->nlags), B = p->B;
+  const int chunk = fdlp::vs_chunk_positions(A, kind == 2);
+  const int nlo = kind == 2 ? T.part_lo[part] : T.smin[kind];
+  const int nhi = kind == 2 ? T.part_hi[part] : p->N;
+  const int kbeg = kind == 2 ? T.part_ev[part] : 0, kend = kind == 2 ? T.part_ev[part + 1] : B;
+  auto S_of = [&](int k) { return kind == 2 ? T.fl[k].S : T.snap[(size_t)kind * B + k].S; };
+  if (info) { info[0] = A; info[1] = chunk; info[2] = nlo; info[3] = nhi; }
+  std::vector<fdlp::VsRec> out;
+  if (nhi <= nlo) {
+    out.push_back({0, fdlp::kVsEnd, nlo, kend - kbeg});
+    return out;
+  }
+  const int b_top = (nhi - 1) / A, b_bot = nlo / A, b_whole = fdlp::vs_whole_top(nhi, A);
+  int lo_loaded = ((A * b_top + 17 * A - 1 + chunk - 1) / chunk) * chunk;
+  int run = 0, k = kbeg;
+  auto emit = [&](int action, int pos, int aux) {
+    out.push_back({run, action, pos, aux});
+    run = 0;
+  };
+  auto ensure = [&](int n0) {
+    while (n0 < lo_loaded) {
+      lo_loaded -= chunk;
+      emit(fdlp::kVsCommit, lo_loaded, 0);
+    }
+  };
+  auto evS = [&]() { return k < kend ? S_of(k) : -1; };
+  auto block = [&](int n0) {
+    ensure(std::max(n0 - A, A * b_bot));
+    const int k0 = k;
+    int hi_m = std::min(n0 + A, nhi);
+    for (;;) {
+      while (evS() >= hi_m) ++k;
+      const int lo_m = std::max(std::max(evS(), n0), nlo);
+      if (lo_m <= n0 || lo_m <= nlo) break;
+      hi_m = lo_m;
+    }
+    emit(fdlp::kVsGeneral, n0, k - k0);
+  };
+  ensure(A * b_top);
+  for (int b = b_top; b >= b_bot;) {
+    for (int m = fdlp::vs_run_pairs(b, b_whole, evS(), lo_loaded, b_bot, A); m > 0; --m) {
+      run += 2;
+      b -= 2;
+    }
+    block(A * b);
+    if (--b < b_bot) break;
+    block(A * b);
+    --b;
+  }
+  emit(fdlp::kVsEnd, nlo, kend - k);
+  return out;
+}
+
+int fdlp_plan_sweep_schedule(const fdlp_plan* p, int32_t kind, int32_t part, int32_t* info, int32_t* nrec,
+                             int32_t* recs, int32_t cap) {
+  if (!p) return fail(FDLP_E_INVALID, "fdlp_plan_sweep_schedule: null plan");
+  if (info) info[0] = info[1] = info[2] = info[3] = 0;
+  if (nrec) *nrec = 0;
+  if (!(p->sk_avail && p->vs_avail)) return FDLP_OK;
+  if (kind < 0 || kind > 2 || part < 0 || part >= (kind == 2 ? p->sk.fl_H : 1))
+    return fail(FDLP_E_INVALID, "fdlp_plan_sweep_schedule: kind is 0, 1 (skirts) or 2 (flat, part < parts)");
+  const std::vector<fdlp::VsRec> s = sweep_schedule(p, kind, part, info);
+  if (nrec) *nrec = (int32_t)s.size();
+  if (recs)
+    for (size_t i = 0; i < s.size() && (int32_t)i < cap; ++i) {
+      recs[4 * i] = s[i].run; recs[4 * i + 1] = s[i].action; recs[4 * i + 2] = s[i].pos; recs[4 * i + 3] = s[i].aux;
+    }
+  return FDLP_OK;
+}
+
 int fdlp_plan_regions(const fdlp_plan* p, int32_t* m1, int32_t* m2) {
   if (!p) return fail(FDLP_E_INVALID, "fdlp_plan_regions: null plan");
   if (!p->sk_avail) return fail(FDLP_E_INVALID, "filterbank has no skirt/flat-top split (structured path unavailable)");

@@ -227,6 +227,20 @@ class FdlpPlan:
         check(lib.fdlp_plan_flat_events(self._h, None, None, ctypes.byref(n), ptr(ev, ctypes.c_int32), n.value))
         return C.value, H.value, ev
 
+    def sweep_schedule(self, kind: int, part: int = 0):
+        """(info, records[n, 4] = (run, action, pos, aux)) of one VALU sweep's walk, top-down: kind 0 / 1 the
+        lower / upper skirt, 2 the flat tops' part `part`.  `run` whole blocks taken without a test, then
+        action 0 commit the chunk at pos, 1 a general block at base pos handling aux events, 2 end of sweep
+        (aux events left).  info = dict(A, chunk, nlo, nhi).  No records when the plan has no VALU sweeps."""
+        info = np.zeros(4, dtype=np.int32)
+        n = _lib.c_i32()
+        check(lib.fdlp_plan_sweep_schedule(self._h, int(kind), int(part), ptr(info, ctypes.c_int32),
+                                           ctypes.byref(n), None, 0))
+        rec = np.zeros((n.value, 4), dtype=np.int32)
+        check(lib.fdlp_plan_sweep_schedule(self._h, int(kind), int(part), None, ctypes.byref(n),
+                                           ptr(rec, ctypes.c_int32), n.value))
+        return dict(zip(("A", "chunk", "nlo", "nhi"), (int(v) for v in info))), rec
+
     def set_pipeline(self, n_sub: int):
         check(lib.fdlp_set_pipeline(self._h, int(n_sub)))
 
