@@ -436,8 +436,11 @@ int fdlp_xform_compute(fdlp_xform_plan* plan, const fdlp_post_batch* batch, cons
  *     FDLP_NNET_SOFTMAX  p_j = exp(x_j - m) / S   (extract_posterior.py --add_softmax; the reference's
  *                        np.exp(X) / sum has no max subtraction and gives NaN above 88: that is not reproduced)
  *     FDLP_NNET_LOGLIKE  ((x_j - m) - log S) - prior_weight * prior[j]   (log_softmax - prior_weight * prior of
- *                        dump_genclassifier_outputs.py:110, what latgen-faster-mapped consumes) */
-#define FDLP_NNET_MAX_LINEAR 32
+ *                        dump_genclassifier_outputs.py:110, what latgen-faster-mapped consumes)
+ * A feed-forward net is the linear-only stage plan: fdlp_nnet_* is a front over fdlp_rnn_* (below) with the stages
+ * FDLP_RNN_LINEAR_RELU x (n_linear - 1), FDLP_RNN_LINEAR, no group table and no limit on the utterances of a batch.
+ * The launches, the evaluation order and the checks are that plan's. */
+#define FDLP_NNET_MAX_LINEAR 32   /* <= FDLP_RNN_MAX_STAGES */
 enum { FDLP_NNET_RAW = 0, FDLP_NNET_SOFTMAX = 1, FDLP_NNET_LOGLIKE = 2 };
 typedef struct fdlp_nnet_config {
   fdlp_post_config post;                    /* the stages before the network (post.device is the plan's device) */

@@ -2090,201 +2090,25 @@ int fdlp_xform_compute(fdlp_xform_plan* x, const fdlp_post_batch* b, const void*
 }
 
 // ---------------------------------------------------------------------------------------------
-// Network plan (cmvn | deltas | splice | nnetFeedforward): a transform plan for layer 0 ([W_0 | b_0], affine),
-// the other layers' weights on the device, and two workspaces the dense layers ping-pong between
+// Stage plan (cmvn | deltas | splice | a list of GRU and linear stages): a transform plan for stage 0 (a linear
+// stage's [W | b] or a GRU's [W_ih | b_ih]), the other weights on the device, the G buffer of the input projections,
+// two workspaces the stages ping-pong between, and the group table of gru_scan_kernel.  fdlp_rnn_* is its public
+// face; fdlp_nnet_* (below it) is the same plan with the stages linear_relu x (n_linear - 1), linear and no scans.
 // ---------------------------------------------------------------------------------------------
-struct fdlp_nnet_plan {
-  fdlp_xform_plan* l0 = nullptr;
-  int n_linear = 0, device = -1;
-  std::vector<int> dims;        // n_linear + 1
-  int64_t max_rows = 0;
-  int max_hidden = 0;           // widest of dims[1 .. n_linear - 1], 0 with one layer
-  float* d_m0 = nullptr;        // [dims[1], dims[0] + 1]
-  std::vector<float*> d_w, d_b; // layers 1 ..; entry 0 unused
-  float* d_ws[2] = {nullptr, nullptr};
+// what a front calls itself and its parts in the messages
+struct StageWords {
+  const char *create, *compute, *model, *stage;
 };
+static const StageWords kRnnWords = {"fdlp_rnn_plan_create", "fdlp_rnn_compute", "model", "stage"};
+static const StageWords kNnetWords = {"fdlp_nnet_plan_create", "fdlp_nnet_compute", "network", "layer"};
 
-static int free_nnet_plan(fdlp_nnet_plan* p) {
-  if (!p) return FDLP_OK;
-  int rc = FDLP_OK;
-  {
-    DeviceGuard dg(p->device);
-    if (p->d_m0) (void)hipFree(p->d_m0);
-    for (float* w : p->d_w)
-      if (w) (void)hipFree(w);
-    for (float* b : p->d_b)
-      if (b) (void)hipFree(b);
-    for (float* w : p->d_ws)
-      if (w) (void)hipFree(w);
-    if (p->l0) rc = fdlp_xform_plan_destroy(p->l0);
-  }
-  delete p;
-  return rc;
-}
-
-int fdlp_nnet_plan_create(const fdlp_nnet_config* cfg, const float* const* weights, const float* const* biases,
-                          int64_t max_rows, fdlp_nnet_plan** out) {
-  if (!cfg || !out) return fail(FDLP_E_INVALID, "fdlp_nnet_plan_create: null argument");
-  *out = nullptr;
-  const int nl = cfg->n_linear;
-  if (nl < 1 || nl > FDLP_NNET_MAX_LINEAR)
-    return fail(FDLP_E_INVALID, "the network needs 1 .. " + std::to_string(FDLP_NNET_MAX_LINEAR) +
-                                    " linear layers, got n_linear = " + std::to_string(nl));
-  std::string shape;
-  for (int l = 0; l <= nl; ++l) shape += (l ? " -> " : "") + std::to_string(cfg->dims[l]);
-  for (int l = 0; l <= nl; ++l)
-    if (cfg->dims[l] < 1)
-      return fail(FDLP_E_INVALID, "network dimension " + std::to_string(l) + " is " + std::to_string(cfg->dims[l]) +
-                                      " (every dimension must be >= 1; dims " + shape + ")");
-  if (max_rows < 1) return fail(FDLP_E_INVALID, "max_rows must be >= 1, got " + std::to_string(max_rows));
-  const bool dev = cfg->post.device >= 0;
-  if (dev && (!weights || !biases)) return fail(FDLP_E_INVALID, "fdlp_nnet_plan_create: null weights or biases");
-  for (int l = 0; dev && l < nl; ++l)
-    if (!weights[l] || !biases[l])
-      return fail(FDLP_E_INVALID, "fdlp_nnet_plan_create: null weights or biases of layer " + std::to_string(l));
-  auto* p = new (std::nothrow) fdlp_nnet_plan;
-  if (!p) return fail(FDLP_E_NOMEM, "out of memory");
-  p->n_linear = nl;
-  p->device = cfg->post.device;
-  p->dims.assign(cfg->dims, cfg->dims + nl + 1);
-  p->max_rows = max_rows;
-  for (int l = 1; l < nl; ++l) p->max_hidden = std::max(p->max_hidden, cfg->dims[l]);
-  p->d_w.assign((size_t)nl, nullptr);
-  p->d_b.assign((size_t)nl, nullptr);
-  int rc;
-#define NNET_FAIL(code, msg) do { rc = fail(code, msg); free_nnet_plan(p); return rc; } while (0)
-#define NNET_TRY(expr)                           \
-  do {                                           \
-    rc = (expr);                                 \
-    if (rc != FDLP_OK) {                         \
-      std::string m_ = fdlp::last_error_slot();  \
-      free_nnet_plan(p);                         \
-      fdlp::last_error_slot() = m_;              \
-      return rc;                                 \
-    }                                            \
-  } while (0)
-  fdlp_xform_config xc{};
-  xc.post = cfg->post;
-  xc.out_dim = cfg->dims[1];
-  xc.affine = 1;
-  NNET_TRY(fdlp_xform_plan_create(&xc, &p->l0));
-  const int K0 = p->l0->post->Dout;
-  if (K0 != cfg->dims[0])
-    NNET_FAIL(FDLP_E_INVALID, "the network's input dimension dims[0] = " + std::to_string(cfg->dims[0]) +
-                                  " differs from the " + std::to_string(K0) + " columns the stages before it give");
-  if (!dev) {
-    *out = p;
-    return FDLP_OK;
-  }
-  DeviceGuard dg(p->device);
-  if (dg.status() != hipSuccess) NNET_FAIL(FDLP_E_HIP, "hipSetDevice failed");
-  {
-    // layer 0 as transform-feats' affine matrix: [W_0 | b_0]
-    const int H = cfg->dims[1];
-    std::vector<float> m0((size_t)H * (K0 + 1));
-    for (int n = 0; n < H; ++n) {
-      memcpy(&m0[(size_t)n * (K0 + 1)], weights[0] + (size_t)n * K0, sizeof(float) * K0);
-      m0[(size_t)n * (K0 + 1) + K0] = biases[0][n];
-    }
-    NNET_TRY(upload(&p->d_m0, m0.data(), m0.size()));
-  }
-  for (int l = 1; l < nl; ++l) {
-    NNET_TRY(upload(&p->d_w[(size_t)l], weights[l], (size_t)cfg->dims[l + 1] * cfg->dims[l]));
-    NNET_TRY(upload(&p->d_b[(size_t)l], biases[l], (size_t)cfg->dims[l + 1]));
-  }
-  if (p->max_hidden > 0) {
-    const size_t n = (size_t)max_rows * p->max_hidden;
-    for (float*& w : p->d_ws) {
-      if (hipMalloc((void**)&w, sizeof(float) * n) != hipSuccess) {
-        w = nullptr;
-        NNET_FAIL(FDLP_E_NOMEM, "network workspace allocation failed: 2 x " + std::to_string(max_rows) + " rows x " +
-                                    std::to_string(p->max_hidden) + " columns of float32");
-      }
-      // rows no utterance covers are read by the dense layers (and never stored into an utterance's rows)
-      if (hipMemset(w, 0, sizeof(float) * n) != hipSuccess) NNET_FAIL(FDLP_E_HIP, "network workspace memset failed");
-    }
-  }
-#undef NNET_TRY
-#undef NNET_FAIL
-  *out = p;
-  return FDLP_OK;
-}
-
-int fdlp_nnet_plan_destroy(fdlp_nnet_plan* p) { return free_nnet_plan(p); }
-
-int fdlp_nnet_plan_info(const fdlp_nnet_plan* p, int32_t* in_dim, int32_t* n_linear, int32_t* out_dims,
-                        int64_t* workspace_bytes, int32_t* tile, int32_t* lds_bytes) {
-  if (!p) return fail(FDLP_E_INVALID, "fdlp_nnet_plan_info: null plan");
-  if (in_dim) *in_dim = p->dims[0];
-  if (n_linear) *n_linear = p->n_linear;
-  if (out_dims)
-    for (int l = 0; l < p->n_linear; ++l) out_dims[l] = p->dims[(size_t)l + 1];
-  if (workspace_bytes) *workspace_bytes = 2 * (int64_t)sizeof(float) * p->max_rows * p->max_hidden;
-  if (tile) {
-    tile[0] = fdlp::kDenseTM;
-    tile[1] = fdlp::kDenseTN;
-    tile[2] = fdlp::kDenseKC;
-  }
-  if (lds_bytes) *lds_bytes = (int32_t)fdlp::dense_lds_bytes(fdlp::kDenseTN);
-  return FDLP_OK;
-}
-
-int fdlp_nnet_compute(fdlp_nnet_plan* p, const fdlp_post_batch* b, int32_t tap, int32_t mode, const void* prior_dev,
-                      float prior_weight, void* stream) {
-  if (!p || !b) return fail(FDLP_E_INVALID, "fdlp_nnet_compute: null argument");
-  if (p->device < 0) return fail(FDLP_E_INVALID, "fdlp_nnet_compute: host-only plan");
-  if (tap < 0 || tap >= p->n_linear)
-    return fail(FDLP_E_INVALID, "tap " + std::to_string(tap) + " is outside 0 .. " + std::to_string(p->n_linear - 1) +
-                                    " (the network has " + std::to_string(p->n_linear - 1) + " hidden layers)");
-  if (mode != FDLP_NNET_RAW && mode != FDLP_NNET_SOFTMAX && mode != FDLP_NNET_LOGLIKE)
-    return fail(FDLP_E_INVALID, "fdlp_nnet_compute: unknown mode " + std::to_string(mode));
-  if (mode != FDLP_NNET_RAW && tap != 0)
-    return fail(FDLP_E_INVALID, "softmax and loglike apply to the last layer only (tap 0), got tap " +
-                                    std::to_string(tap));
-  if (mode == FDLP_NNET_LOGLIKE && (!prior_dev || ((uintptr_t)prior_dev & 3u)))
-    return fail(FDLP_E_INVALID, "loglike needs a 4-byte aligned device prior vector");
-  if (b->n_rows > p->max_rows)
-    return fail(FDLP_E_CAPACITY, "batch of " + std::to_string(b->n_rows) + " rows exceeds the plan's max_rows " +
-                                     std::to_string(p->max_rows));
-  if (b->n_utt > 0 && (!b->out_dev || ((uintptr_t)b->out_dev & 3u)))
-    return fail(FDLP_E_INVALID, "fdlp_nnet_compute: out_dev must be a 4-byte aligned device pointer");
-  const int last = p->n_linear - 1 - tap;  // the tapped layer
-  hipStream_t s = (hipStream_t)stream;
-  // layer 0 in the chain's launch; its batch checks are the chain's
-  fdlp_post_batch b0 = *b;
-  if (last > 0) b0.out_dev = p->d_ws[0];
-  fdlp::XformConsts xc{};
-  xc.N = p->dims[1]; xc.C = p->dims[0] + 1; xc.affine = 1; xc.n_mat = 1;
-  {
-    const int rc = post_compute(p->l0->post, &b0, stream, &xc, p->d_m0, nullptr);
-    if (rc != FDLP_OK) return rc;
-  }
-  if (b->n_utt == 0 || b->n_rows == 0) return FDLP_OK;
-  DeviceGuard dg(p->device);
-  HIP_TRY(dg.status());
-  for (int l = 1; l <= last; ++l) {
-    const float* in = p->d_ws[(l - 1) & 1];
-    float* o = l == last ? (float*)b->out_dev : p->d_ws[l & 1];
-    HIP_TRY(fdlp::launch_dense(in, p->d_w[(size_t)l], p->d_b[(size_t)l], o, b->n_rows, p->dims[(size_t)l],
-                               p->dims[(size_t)l + 1], 1, s));
-  }
-  if (mode != FDLP_NNET_RAW)
-    HIP_TRY(fdlp::launch_row_epilogue((float*)b->out_dev, b->n_rows, p->dims[(size_t)p->n_linear], mode,
-                                      (const float*)prior_dev, prior_weight, s));
-  return FDLP_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Recurrent plan (cmvn | deltas | splice | GRU stack): a transform plan for stage 0 (a linear stage's [W | b] or a
-// GRU's [W_ih | b_ih]), the other weights on the device, the G buffer of the input projections, two workspaces the
-// stages ping-pong between, and the group table of gru_scan_kernel
-// ---------------------------------------------------------------------------------------------
 struct fdlp_rnn_plan {
+  const StageWords* words = &kRnnWords;
   fdlp_xform_plan* l0 = nullptr;
   int n_stages = 0, device = -1;
   std::vector<int> kind, dims;  // n_stages, n_stages + 1
   int64_t max_rows = 0;
-  int max_utts = 0, max_groups = 0;
+  int max_utts = 0, max_groups = 0;  // both 0 behind the nnet front: no scans, no group table, any n_utt
   int max_h = 0;                // widest GRU, 0 without one
   int widest = 0;               // widest of dims[1 .. n_stages - 1], 0 with one stage
   float* d_m0 = nullptr;        // [N_0, dims[0] + 1], N_0 = dims[1] or 3 dims[1]
@@ -2338,9 +2162,25 @@ static std::vector<int> rnn_group_order(const int64_t* len, int n) {
   return order;
 }
 
-int fdlp_rnn_plan_create(const fdlp_rnn_config* cfg, const float* const* params, int64_t max_rows, int32_t max_utts,
-                         fdlp_rnn_plan** out) {
-  if (!cfg || !out) return fail(FDLP_E_INVALID, "fdlp_rnn_plan_create: null argument");
+// Frees a half-built plan when create returns early; the message of the error that ended it survives the free
+struct StagePlanGuard {
+  fdlp_rnn_plan* p;
+  ~StagePlanGuard() {
+    if (!p) return;
+    const std::string m = fdlp::last_error_slot();
+    free_rnn_plan(p);
+    fdlp::last_error_slot() = m;
+  }
+  fdlp_rnn_plan* release() {
+    fdlp_rnn_plan* q = p;
+    p = nullptr;
+    return q;
+  }
+};
+
+// max_utts = 0 (the nnet front; legal without a GRU only): no scans, so no group table, staging or event
+static int stage_plan_create(const fdlp_rnn_config* cfg, const float* const* params, int64_t max_rows,
+                             int32_t max_utts, const StageWords& w, fdlp_rnn_plan** out) {
   *out = nullptr;
   const int ns = cfg->n_stages;
   if (ns < 1 || ns > FDLP_RNN_MAX_STAGES)
@@ -2354,26 +2194,30 @@ int fdlp_rnn_plan_create(const fdlp_rnn_config* cfg, const float* const* params,
                                       std::to_string(cfg->kind[s]) + " (0 GRU, 1 linear, 2 linear with ReLU)");
   for (int s = 0; s <= ns; ++s)
     if (cfg->dims[s] < 1)
-      return fail(FDLP_E_INVALID, "model dimension " + std::to_string(s) + " is " + std::to_string(cfg->dims[s]) +
-                                      " (every dimension must be >= 1; dims " + shape + ")");
+      return fail(FDLP_E_INVALID, std::string(w.model) + " dimension " + std::to_string(s) + " is " +
+                                      std::to_string(cfg->dims[s]) + " (every dimension must be >= 1; dims " + shape +
+                                      ")");
   if (max_rows < 1) return fail(FDLP_E_INVALID, "max_rows must be >= 1, got " + std::to_string(max_rows));
-  if (max_utts < 1) return fail(FDLP_E_INVALID, "max_utts must be >= 1, got " + std::to_string(max_utts));
   int max_h = 0;
   for (int s = 0; s < ns; ++s)
     if (cfg->kind[s] == FDLP_RNN_GRU) max_h = std::max(max_h, cfg->dims[s + 1]);
+  if (max_utts < (max_h > 0 ? 1 : 0))
+    return fail(FDLP_E_INVALID, "max_utts must be >= 1, got " + std::to_string(max_utts));
   if (max_h > fdlp::gru_max_hidden())
     return fail(FDLP_E_INVALID, "a GRU of " + std::to_string(max_h) + " hidden units needs " +
                                     std::to_string(fdlp::gru_lds_bytes(max_h)) + " bytes of the 163840-byte LDS; the "
                                     "widest that fits has " + std::to_string(fdlp::gru_max_hidden()));
   const bool dev = cfg->post.device >= 0;
-  if (dev && !params) return fail(FDLP_E_INVALID, "fdlp_rnn_plan_create: null params");
+  if (dev && !params) return fail(FDLP_E_INVALID, std::string(w.create) + ": null parameters");
   for (int s = 0; dev && s < ns; ++s) {
     const bool gru = cfg->kind[s] == FDLP_RNN_GRU;
     if (!params[4 * s] || !params[4 * s + 2] || (gru && (!params[4 * s + 1] || !params[4 * s + 3])))
-      return fail(FDLP_E_INVALID, "fdlp_rnn_plan_create: null parameters of stage " + std::to_string(s));
+      return fail(FDLP_E_INVALID, std::string(w.create) + ": null parameters of " + w.stage + " " + std::to_string(s));
   }
   auto* p = new (std::nothrow) fdlp_rnn_plan;
   if (!p) return fail(FDLP_E_NOMEM, "out of memory");
+  StagePlanGuard guard{p};
+  p->words = &w;
   p->n_stages = ns;
   p->device = cfg->post.device;
   p->kind.assign(cfg->kind, cfg->kind + ns);
@@ -2385,33 +2229,23 @@ int fdlp_rnn_plan_create(const fdlp_rnn_config* cfg, const float* const* params,
   for (int s = 1; s < ns; ++s) p->widest = std::max(p->widest, cfg->dims[s]);
   p->d_p.assign((size_t)ns * 4, nullptr);
   int rc;
-#define RNN_FAIL(code, msg) do { rc = fail(code, msg); free_rnn_plan(p); return rc; } while (0)
-#define RNN_TRY(expr)                            \
-  do {                                           \
-    rc = (expr);                                 \
-    if (rc != FDLP_OK) {                         \
-      std::string m_ = fdlp::last_error_slot();  \
-      free_rnn_plan(p);                          \
-      fdlp::last_error_slot() = m_;              \
-      return rc;                                 \
-    }                                            \
-  } while (0)
   const int N0 = cfg->kind[0] == FDLP_RNN_GRU ? 3 * cfg->dims[1] : cfg->dims[1];
   fdlp_xform_config xc{};
   xc.post = cfg->post;
   xc.out_dim = N0;
   xc.affine = 1;
-  RNN_TRY(fdlp_xform_plan_create(&xc, &p->l0));
+  if ((rc = fdlp_xform_plan_create(&xc, &p->l0)) != FDLP_OK) return rc;
   const int K0 = p->l0->post->Dout;
   if (K0 != cfg->dims[0])
-    RNN_FAIL(FDLP_E_INVALID, "the model's input dimension dims[0] = " + std::to_string(cfg->dims[0]) +
-                                 " differs from the " + std::to_string(K0) + " columns the stages before it give");
+    return fail(FDLP_E_INVALID, std::string("the ") + w.model + "'s input dimension dims[0] = " +
+                                    std::to_string(cfg->dims[0]) + " differs from the " + std::to_string(K0) +
+                                    " columns the stages before it give");
   if (!dev) {
-    *out = p;
+    *out = guard.release();
     return FDLP_OK;
   }
   DeviceGuard dg(p->device);
-  if (dg.status() != hipSuccess) RNN_FAIL(FDLP_E_HIP, "hipSetDevice failed");
+  if (dg.status() != hipSuccess) return fail(FDLP_E_HIP, "hipSetDevice failed");
   {
     // stage 0's input side as transform-feats' affine matrix: [W | b]
     std::vector<float> m0((size_t)N0 * (K0 + 1));
@@ -2419,50 +2253,46 @@ int fdlp_rnn_plan_create(const fdlp_rnn_config* cfg, const float* const* params,
       memcpy(&m0[(size_t)n * (K0 + 1)], params[0] + (size_t)n * K0, sizeof(float) * K0);
       m0[(size_t)n * (K0 + 1) + K0] = params[2][n];
     }
-    RNN_TRY(upload(&p->d_m0, m0.data(), m0.size()));
+    if ((rc = upload(&p->d_m0, m0.data(), m0.size())) != FDLP_OK) return rc;
   }
   for (int s = 0; s < ns; ++s) {
-    const int K = cfg->dims[s], N = cfg->dims[s + 1];
+    const size_t K = (size_t)cfg->dims[s], N = (size_t)cfg->dims[s + 1];
     const bool gru = cfg->kind[s] == FDLP_RNN_GRU;
-    if (s > 0) {
-      RNN_TRY(upload(&p->d_p[4 * (size_t)s], params[4 * s], (size_t)(gru ? 3 * N : N) * K));
-      RNN_TRY(upload(&p->d_p[4 * (size_t)s + 2], params[4 * s + 2], (size_t)(gru ? 3 * N : N)));
-    }
-    if (gru) {
-      RNN_TRY(upload(&p->d_p[4 * (size_t)s + 1], params[4 * s + 1], (size_t)3 * N * N));
-      RNN_TRY(upload(&p->d_p[4 * (size_t)s + 3], params[4 * s + 3], (size_t)3 * N));
-    }
+    // w_ih | w, w_hh, b_ih | b, b_hh; stage 0's input side is d_m0
+    const size_t count[4] = {s > 0 ? (gru ? 3 * N : N) * K : 0, gru ? 3 * N * N : 0, s > 0 ? (gru ? 3 * N : N) : 0,
+                             gru ? 3 * N : 0};
+    for (int i : {0, 2, 1, 3})  // the input side first
+      if (count[i] && (rc = upload(&p->d_p[4 * (size_t)s + i], params[4 * s + i], count[i])) != FDLP_OK) return rc;
   }
-  auto zeroed = [&](float** w, size_t n, const char* what) -> int {
+  auto zeroed = [&](float** ws, size_t n, const char* what) -> int {
     if (n == 0) return FDLP_OK;
-    if (hipMalloc((void**)w, sizeof(float) * n) != hipSuccess) {
-      *w = nullptr;
-      return fail(FDLP_E_NOMEM, std::string("recurrent plan: allocation of ") + what + " failed: " +
-                                    std::to_string(n) + " float32 for " + std::to_string(max_rows) + " rows");
+    if (hipMalloc((void**)ws, sizeof(float) * n) != hipSuccess) {
+      *ws = nullptr;
+      return fail(FDLP_E_NOMEM, std::string("stage plan: allocation of ") + what + " failed: " + std::to_string(n) +
+                                    " float32 for " + std::to_string(max_rows) + " rows");
     }
     // rows no utterance covers are read by the dense launches (and never stored into an utterance's rows)
-    if (hipMemset(*w, 0, sizeof(float) * n) != hipSuccess) return fail(FDLP_E_HIP, "recurrent plan: memset failed");
+    if (hipMemset(*ws, 0, sizeof(float) * n) != hipSuccess) return fail(FDLP_E_HIP, "stage plan: memset failed");
     return FDLP_OK;
   };
-  RNN_TRY(zeroed(&p->d_g, (size_t)max_rows * 3 * p->max_h, "the projection buffer"));
-  for (float*& w : p->d_ws) RNN_TRY(zeroed(&w, (size_t)max_rows * p->widest, "a stage workspace"));
-  const size_t nslots = (size_t)p->max_groups * fdlp::kGruGU;
-  if (hipMalloc((void**)&p->d_slots, sizeof(fdlp::GruSlot) * nslots) != hipSuccess ||
-      hipHostMalloc((void**)&p->h_slots, sizeof(fdlp::GruSlot) * nslots, hipHostMallocDefault) != hipSuccess)
-    RNN_FAIL(FDLP_E_NOMEM, "recurrent plan: group table allocation failed");
-  if (hipEventCreateWithFlags(&p->staging_done, hipEventDisableTiming) != hipSuccess)
-    RNN_FAIL(FDLP_E_NOMEM, "recurrent plan: event creation failed");
-#undef RNN_TRY
-#undef RNN_FAIL
-  *out = p;
+  if ((rc = zeroed(&p->d_g, (size_t)max_rows * 3 * p->max_h, "the projection buffer")) != FDLP_OK) return rc;
+  for (float*& ws : p->d_ws)
+    if ((rc = zeroed(&ws, (size_t)max_rows * p->widest, "a stage workspace")) != FDLP_OK) return rc;
+  if (p->max_groups > 0) {
+    const size_t nslots = (size_t)p->max_groups * fdlp::kGruGU;
+    if (hipMalloc((void**)&p->d_slots, sizeof(fdlp::GruSlot) * nslots) != hipSuccess ||
+        hipHostMalloc((void**)&p->h_slots, sizeof(fdlp::GruSlot) * nslots, hipHostMallocDefault) != hipSuccess)
+      return fail(FDLP_E_NOMEM, "stage plan: group table allocation failed");
+    if (hipEventCreateWithFlags(&p->staging_done, hipEventDisableTiming) != hipSuccess)
+      return fail(FDLP_E_NOMEM, "stage plan: event creation failed");
+  }
+  *out = guard.release();
   return FDLP_OK;
 }
 
-int fdlp_rnn_plan_destroy(fdlp_rnn_plan* p) { return free_rnn_plan(p); }
-
-int fdlp_rnn_plan_info(const fdlp_rnn_plan* p, int32_t* in_dim, int32_t* n_stages, int32_t* out_dims,
-                       int64_t* workspace_bytes, int32_t* group_utts, int32_t* lds_bytes) {
-  if (!p) return fail(FDLP_E_INVALID, "fdlp_rnn_plan_info: null plan");
+// in_dim, the number of stages, their widths and the workspace bytes: what both fronts' info calls share
+static void stage_plan_sizes(const fdlp_rnn_plan* p, int32_t* in_dim, int32_t* n_stages, int32_t* out_dims,
+                             int64_t* workspace_bytes) {
   if (in_dim) *in_dim = p->dims[0];
   if (n_stages) *n_stages = p->n_stages;
   if (out_dims)
@@ -2470,6 +2300,22 @@ int fdlp_rnn_plan_info(const fdlp_rnn_plan* p, int32_t* in_dim, int32_t* n_stage
   if (workspace_bytes)
     *workspace_bytes = (int64_t)sizeof(float) * p->max_rows * (3 * (int64_t)p->max_h + 2 * (int64_t)p->widest) +
                        (int64_t)sizeof(fdlp::GruSlot) * p->max_groups * fdlp::kGruGU;
+}
+
+int fdlp_rnn_plan_create(const fdlp_rnn_config* cfg, const float* const* params, int64_t max_rows, int32_t max_utts,
+                         fdlp_rnn_plan** out) {
+  if (!cfg || !out) return fail(FDLP_E_INVALID, "fdlp_rnn_plan_create: null argument");
+  *out = nullptr;
+  if (max_utts < 1) return fail(FDLP_E_INVALID, "max_utts must be >= 1, got " + std::to_string(max_utts));
+  return stage_plan_create(cfg, params, max_rows, max_utts, kRnnWords, out);
+}
+
+int fdlp_rnn_plan_destroy(fdlp_rnn_plan* p) { return free_rnn_plan(p); }
+
+int fdlp_rnn_plan_info(const fdlp_rnn_plan* p, int32_t* in_dim, int32_t* n_stages, int32_t* out_dims,
+                       int64_t* workspace_bytes, int32_t* group_utts, int32_t* lds_bytes) {
+  if (!p) return fail(FDLP_E_INVALID, "fdlp_rnn_plan_info: null plan");
+  stage_plan_sizes(p, in_dim, n_stages, out_dims, workspace_bytes);
   if (group_utts) *group_utts = fdlp::kGruGU;
   if (lds_bytes) *lds_bytes = p->max_h ? (int32_t)fdlp::gru_lds_bytes(p->max_h) : 0;
   return FDLP_OK;
@@ -2514,30 +2360,35 @@ int fdlp_rnn_times(fdlp_rnn_plan* p, double* ms) {
   return FDLP_OK;
 }
 
-int fdlp_rnn_compute(fdlp_rnn_plan* p, const fdlp_post_batch* b, int32_t tap, int32_t mode, const void* prior_dev,
-                     float prior_weight, void* stream) {
-  if (!p || !b) return fail(FDLP_E_INVALID, "fdlp_rnn_compute: null argument");
-  if (p->device < 0) return fail(FDLP_E_INVALID, "fdlp_rnn_compute: host-only plan");
+static int stage_compute(fdlp_rnn_plan* p, const fdlp_post_batch* b, int32_t tap, int32_t mode, const void* prior_dev,
+                         float prior_weight, void* stream) {
+  const StageWords& words = *p->words;
+  auto who = [&](const char* what) { return std::string(words.compute) + ": " + what; };  // built on refusal only
+  if (p->device < 0) return fail(FDLP_E_INVALID, who("host-only plan"));
   if (tap < 0 || tap >= p->n_stages)
     return fail(FDLP_E_INVALID, "tap " + std::to_string(tap) + " is outside 0 .. " + std::to_string(p->n_stages - 1) +
-                                    " (the model has " + std::to_string(p->n_stages) + " stages)");
+                                    " (the " + words.model + " has " + std::to_string(p->n_stages) + " " +
+                                    words.stage + "s)");
   if (mode != FDLP_NNET_RAW && mode != FDLP_NNET_SOFTMAX && mode != FDLP_NNET_LOGLIKE)
-    return fail(FDLP_E_INVALID, "fdlp_rnn_compute: unknown mode " + std::to_string(mode));
+    return fail(FDLP_E_INVALID, who("unknown mode ") + std::to_string(mode));
   if (mode != FDLP_NNET_RAW && tap != 0)
-    return fail(FDLP_E_INVALID, "softmax and loglike apply to the last stage only (tap 0), got tap " +
-                                    std::to_string(tap));
+    return fail(FDLP_E_INVALID, std::string("softmax and loglike apply to the last ") + words.stage +
+                                    " only (tap 0), got tap " + std::to_string(tap));
   if (mode == FDLP_NNET_LOGLIKE && (!prior_dev || ((uintptr_t)prior_dev & 3u)))
     return fail(FDLP_E_INVALID, "loglike needs a 4-byte aligned device prior vector");
-  if (b->n_utt > p->max_utts)
+  if (p->max_utts > 0 && b->n_utt > p->max_utts)
     return fail(FDLP_E_INVALID, "batch of " + std::to_string(b->n_utt) + " utterances exceeds the plan's max_utts " +
                                     std::to_string(p->max_utts));
   if (b->n_rows > p->max_rows)
     return fail(FDLP_E_CAPACITY, "batch of " + std::to_string(b->n_rows) + " rows exceeds the plan's max_rows " +
                                      std::to_string(p->max_rows));
-  if (b->n_utt > 0 && (!b->out_dev || ((uintptr_t)b->out_dev & 3u) || !b->row_off || !b->utt_len))
-    return fail(FDLP_E_INVALID, "fdlp_rnn_compute: bad batch (out_dev must be a 4-byte aligned device pointer)");
-  // the scans index G and the stage outputs through the group table: every utterance inside the batch's rows
-  for (int u = 0; u < b->n_utt; ++u) {
+  if (b->n_utt > 0 && (!b->out_dev || ((uintptr_t)b->out_dev & 3u)))
+    return fail(FDLP_E_INVALID, who("out_dev must be a 4-byte aligned device pointer"));
+  // the scans index G and the stage outputs through the group table: every utterance inside the batch's rows (a
+  // plan without a GRU leaves its batch to the chain's checks alone)
+  const int n_scanned = p->max_h > 0 ? b->n_utt : 0;
+  if (n_scanned > 0 && (!b->row_off || !b->utt_len)) return fail(FDLP_E_INVALID, who("bad batch"));
+  for (int u = 0; u < n_scanned; ++u) {
     const int64_t T = b->utt_len[u], r0 = b->row_off[u];
     if (T < 1 || T > p->max_rows || T > INT32_MAX || r0 < 0 || r0 > b->n_rows - T)
       return fail(FDLP_E_INVALID, "utterance " + std::to_string(u) + " has length " + std::to_string(T) +
@@ -2617,6 +2468,67 @@ int fdlp_rnn_compute(fdlp_rnn_plan* p, const fdlp_post_batch* b, int32_t tap, in
     HIP_TRY(fdlp::launch_row_epilogue((float*)b->out_dev, b->n_rows, p->dims[(size_t)p->n_stages], mode,
                                       (const float*)prior_dev, prior_weight, s));
   return FDLP_OK;
+}
+
+int fdlp_rnn_compute(fdlp_rnn_plan* p, const fdlp_post_batch* b, int32_t tap, int32_t mode, const void* prior_dev,
+                     float prior_weight, void* stream) {
+  if (!p || !b) return fail(FDLP_E_INVALID, "fdlp_rnn_compute: null argument");
+  return stage_compute(p, b, tap, mode, prior_dev, prior_weight, stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Network plan (cmvn | deltas | splice | nnetFeedforward): the stage plan with the stages linear_relu x
+// (n_linear - 1), linear.  fdlp_nnet_plan is that plan under the name include/fdlp.h gives this front.
+// ---------------------------------------------------------------------------------------------
+static fdlp_rnn_plan* stage_plan(fdlp_nnet_plan* p) { return reinterpret_cast<fdlp_rnn_plan*>(p); }
+
+int fdlp_nnet_plan_create(const fdlp_nnet_config* cfg, const float* const* weights, const float* const* biases,
+                          int64_t max_rows, fdlp_nnet_plan** out) {
+  static_assert(FDLP_NNET_MAX_LINEAR <= FDLP_RNN_MAX_STAGES, "a layer is a stage");
+  if (!cfg || !out) return fail(FDLP_E_INVALID, "fdlp_nnet_plan_create: null argument");
+  *out = nullptr;
+  const int nl = cfg->n_linear;
+  if (nl < 1 || nl > FDLP_NNET_MAX_LINEAR)
+    return fail(FDLP_E_INVALID, "the network needs 1 .. " + std::to_string(FDLP_NNET_MAX_LINEAR) +
+                                    " linear layers, got n_linear = " + std::to_string(nl));
+  fdlp_rnn_config sc{};
+  sc.post = cfg->post;
+  sc.n_stages = nl;
+  for (int l = 0; l < nl; ++l) sc.kind[l] = l + 1 < nl ? FDLP_RNN_LINEAR_RELU : FDLP_RNN_LINEAR;
+  std::copy(cfg->dims, cfg->dims + nl + 1, sc.dims);
+  std::vector<const float*> params;
+  if (weights && biases) {
+    params.assign(4 * (size_t)nl, nullptr);
+    for (int l = 0; l < nl; ++l) {
+      params[4 * (size_t)l] = weights[l];
+      params[4 * (size_t)l + 2] = biases[l];
+    }
+  }
+  fdlp_rnn_plan* p = nullptr;
+  const int rc = stage_plan_create(&sc, params.empty() ? nullptr : params.data(), max_rows, 0, kNnetWords, &p);
+  *out = reinterpret_cast<fdlp_nnet_plan*>(p);
+  return rc;
+}
+
+int fdlp_nnet_plan_destroy(fdlp_nnet_plan* p) { return free_rnn_plan(stage_plan(p)); }
+
+int fdlp_nnet_plan_info(const fdlp_nnet_plan* p, int32_t* in_dim, int32_t* n_linear, int32_t* out_dims,
+                        int64_t* workspace_bytes, int32_t* tile, int32_t* lds_bytes) {
+  if (!p) return fail(FDLP_E_INVALID, "fdlp_nnet_plan_info: null plan");
+  stage_plan_sizes(stage_plan(const_cast<fdlp_nnet_plan*>(p)), in_dim, n_linear, out_dims, workspace_bytes);
+  if (tile) {
+    tile[0] = fdlp::kDenseTM;
+    tile[1] = fdlp::kDenseTN;
+    tile[2] = fdlp::kDenseKC;
+  }
+  if (lds_bytes) *lds_bytes = (int32_t)fdlp::dense_lds_bytes(fdlp::kDenseTN);
+  return FDLP_OK;
+}
+
+int fdlp_nnet_compute(fdlp_nnet_plan* p, const fdlp_post_batch* b, int32_t tap, int32_t mode, const void* prior_dev,
+                      float prior_weight, void* stream) {
+  if (!p || !b) return fail(FDLP_E_INVALID, "fdlp_nnet_compute: null argument");
+  return stage_compute(stage_plan(p), b, tap, mode, prior_dev, prior_weight, stream);
 }
 
 int fdlp_reverb(const fdlp_reverb_batch* b, void* stream) {

@@ -21,7 +21,10 @@ time on the CPU.
     reference raises a NameError there, extract_posterior.py:42-51; the data-prep script plainly means raw).
   * The ark values are rounded like dict2Ark's '%.3f' text ark read back by copy-feats, by the rule include/fdlp.h
     documents for ark_decimals: k = nearbyint(v * 10^d), stored as (float)(k / 10^d).
-Out of scope: training.  The GRU models of src/nnet (dump_genclassifier_outputs.py) are in rnn.py.
+Out of scope: training.  The GRU models of src/nnet (dump_genclassifier_outputs.py) are in rnn.py, on what this
+module shares with it: StagePlan (the library has one stage plan; a feed-forward net is its linear-only case),
+NnetRunner on post.py's two-slot loop, the checkpoint and egs.config readers, and run_model_tool, the body of both
+command lines.
 """
 import argparse
 import ctypes
@@ -35,18 +38,72 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import FdlpNnetConfigC, check, lib, ptr
-from .cmvn import MatReader, read_kaldi_dmatrix
-from .post import FeatWriter, PostConfig, XformPlan, _make_batch, _Slot, _split_specifier, cmvn_norm, read_kaldi_matrix
+from ._lib import FdlpNnetConfigC, check, lib
+from .cmvn import read_kaldi_dmatrix
+from .post import (FeatWriter, PostConfig, SlotRunner, XformPlan, _make_batch, _Slot, _split_specifier, cmvn_norm,
+                   read_dmatrix_table, read_kaldi_matrix)
 
 MODES = {"raw": _lib.FDLP_NNET_RAW, "softmax": _lib.FDLP_NNET_SOFTMAX, "loglike": _lib.FDLP_NNET_LOGLIKE}
 
 
-class NnetPlan:
-    """cmvn | deltas | splice | feed-forward network.  weights[l]: float32 [dims[l+1], dims[l]] (nn.Linear's layout),
+class StagePlan:
+    """What NnetPlan and RnnPlan (rnn.py) share: one stage plan of the library under two names.  A constructor sets
+    cfg, _h, dims and out_dim; the class names the C functions behind the handle and the words of its messages."""
+    _DESTROY = _COMPUTE = None
+    _WORDS = ("model", "stage")
+
+    def close(self):
+        h = getattr(self, "_h", None)
+        if h and lib is not None:   # lib is gone when the interpreter shuts down
+            getattr(lib, self._DESTROY)(h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    def tap_dim(self, tap: int) -> int:
+        """columns of the output for `tap` (0: the last stage; s: stage n - 1 - s of n; for a network, tap l is the
+        reference's embeds[-l])"""
+        n, (model, stage) = len(self.dims) - 1, self._WORDS
+        if not 0 <= tap < n:
+            raise ValueError("tap %d is outside 0 .. %d (the %s has %d %ss)" % (tap, n - 1, model, n, stage))
+        return self.dims[n - tap]
+
+    def compute(self, feats: torch.Tensor, lengths: Sequence[int], norm: Optional[torch.Tensor] = None,
+                norm_index: Optional[Sequence[int]] = None, norm_vars: bool = True, tap: int = 0, mode: str = "raw",
+                prior: Optional[torch.Tensor] = None, prior_weight: float = 0.8,
+                offsets: Optional[Sequence[int]] = None, out: Optional[torch.Tensor] = None, stream=None) -> torch.Tensor:
+        """feats, lengths, norm, norm_index, norm_vars, offsets, out as for PostPlan.compute.  tap 0: the last stage's
+        output, in `mode` raw, softmax or loglike (the last with prior, a float32 device tensor [out_dim]); tap s > 0:
+        the output of stage n - 1 - s, raw (of a linear_relu stage or a hidden layer, the pre-activation).  Returns
+        out [rows, tap_dim(tap)]."""
+        who = type(self).__name__ + ".compute"
+        if mode not in MODES:
+            raise ValueError("mode must be one of %s" % ", ".join(MODES))
+        b, out, keep = _make_batch(who, self.cfg.dim, self.tap_dim(tap), feats, lengths, norm, norm_index, norm_vars,
+                                   offsets, out)
+        pp = None
+        if mode == "loglike":
+            if (not isinstance(prior, torch.Tensor) or prior.dtype != torch.float32 or prior.device != feats.device
+                    or tuple(prior.shape) != (self.out_dim,)):
+                raise ValueError("%s: loglike needs prior, a float32 [%d] tensor on the features' device"
+                                 % (who, self.out_dim))
+            prior = prior.contiguous()
+            pp = ctypes.c_void_p(prior.data_ptr())
+        s = stream if stream is not None else torch.cuda.current_stream(feats.device)
+        check(getattr(lib, self._COMPUTE)(self._h, ctypes.byref(b), int(tap), MODES[mode], pp, float(prior_weight),
+                                          ctypes.c_void_p(s.cuda_stream)))
+        return out
+
+
+class NnetPlan(StagePlan):
+    """cmvn | deltas | splice | feed-forward network: the stage plan with the stages linear_relu x (n_linear - 1),
+    linear.  weights[l]: float32 [dims[l+1], dims[l]] (nn.Linear's layout),
     biases[l]: [dims[l+1]], dims[0] being the row width the stages of cfg give.  device=-1 gives a host-only plan
     (dims, workspace_bytes, tile, lds_bytes); it needs the shapes only, so the arrays may be None there and `dims`
     is given instead."""
+    _DESTROY, _COMPUTE = "fdlp_nnet_plan_destroy", "fdlp_nnet_compute"
+    _WORDS = ("network", "layer")
 
     def __init__(self, cfg: PostConfig, weights, biases, max_rows: int = 16384, device: int = 0,
                  dims: Optional[Sequence[int]] = None):
@@ -89,46 +146,6 @@ class NnetPlan:
         self.out_dim = self.dims[-1]
         self.workspace_bytes, self.tile, self.lds_bytes = wsb.value, tuple(tile), lds.value
 
-    def close(self):
-        h = getattr(self, "_h", None)
-        if h:
-            lib.fdlp_nnet_plan_destroy(h)
-            self._h = None
-
-    def __del__(self):
-        self.close()
-
-    def tap_dim(self, tap: int) -> int:
-        """columns of the output for `tap` (0: the last layer; l: the reference's embeds[-l])"""
-        if not 0 <= tap < self.n_linear:
-            raise ValueError("tap %d is outside 0 .. %d (the network has %d hidden layers)"
-                             % (tap, self.n_linear - 1, self.n_linear - 1))
-        return self.dims[self.n_linear - tap]
-
-    def compute(self, feats: torch.Tensor, lengths: Sequence[int], norm: Optional[torch.Tensor] = None,
-                norm_index: Optional[Sequence[int]] = None, norm_vars: bool = True, tap: int = 0, mode: str = "raw",
-                prior: Optional[torch.Tensor] = None, prior_weight: float = 0.8,
-                offsets: Optional[Sequence[int]] = None, out: Optional[torch.Tensor] = None, stream=None) -> torch.Tensor:
-        """feats, lengths, norm, norm_index, norm_vars, offsets, out as for PostPlan.compute.  tap 0: the last layer's
-        output, in `mode` raw, softmax or loglike (the last with prior, a float32 device tensor [out_dim]); tap l > 0:
-        the pre-activation of hidden layer n_hidden - l + 1, raw.  Returns out [rows, tap_dim(tap)]."""
-        if mode not in MODES:
-            raise ValueError("mode must be one of %s" % ", ".join(MODES))
-        b, out, keep = _make_batch("NnetPlan.compute", self.cfg.dim, self.tap_dim(tap), feats, lengths, norm,
-                                   norm_index, norm_vars, offsets, out)
-        pp = None
-        if mode == "loglike":
-            if (not isinstance(prior, torch.Tensor) or prior.dtype != torch.float32 or prior.device != feats.device
-                    or tuple(prior.shape) != (self.out_dim,)):
-                raise ValueError("NnetPlan.compute: loglike needs prior, a float32 [%d] tensor on the features' device"
-                                 % self.out_dim)
-            prior = prior.contiguous()
-            pp = ctypes.c_void_p(prior.data_ptr())
-        s = stream if stream is not None else torch.cuda.current_stream(feats.device)
-        check(lib.fdlp_nnet_compute(self._h, ctypes.byref(b), int(tap), MODES[mode], pp, float(prior_weight),
-                                    ctypes.c_void_p(s.cuda_stream)))
-        return out
-
 
 # ---------------------------------------------------------------------------------------------
 # the reference's files: the checkpoint dict of train_feedforward*.py and egs.config
@@ -151,47 +168,58 @@ class FeedforwardCheckpoint:
 HEADER_KEYS = ("feature_dim", "num_frames", "num_layers", "hidden_dim", "num_classes")
 
 
-def load_feedforward_checkpoint(path: str) -> FeedforwardCheckpoint:
-    """torch.load of the dict the reference's trainers save: feature_dim, num_frames, num_layers, hidden_dim,
-    num_classes and model_state_dict with layers.{i}.weight / layers.{i}.bias, i = 0 .. num_layers.  Every shape is
-    checked against the header; the errors name the key."""
+def open_checkpoint(path: str, keys: Sequence[str], zero_ok: Sequence[str] = (), hint: str = ""):
+    """(header, model_state_dict) of a dict the reference's trainers save: header[k] = int(d[k]) for k in keys, each
+    >= 1, or >= 0 for those of zero_ok.  A missing file is an OSError that names it; everything else a ValueError
+    that names the path and the key (`hint` is appended where a key is missing)."""
+    with open(path, "rb"):   # a missing or unreadable file is an OSError that names it
+        pass
     try:
         d = torch.load(path, map_location="cpu")
-    except (OSError, IOError):
-        raise
-    except Exception as e:  # an unpickling error of any kind
+    except Exception as e:  # an unpickling error of any kind; a truncated archive surfaces as an OSError without a name
         raise ValueError("%s: not a torch checkpoint (%s)" % (path, e))
     if not isinstance(d, dict):
         raise ValueError("%s: the checkpoint is a %s, not a dict" % (path, type(d).__name__))
-    for k in HEADER_KEYS + ("model_state_dict",):
+    for k in tuple(keys) + ("model_state_dict",):
         if k not in d:
-            raise ValueError("%s: the checkpoint has no key '%s'" % (path, k))
+            raise ValueError("%s: the checkpoint has no key '%s'%s" % (path, k, hint))
     hdr = {}
-    for k in HEADER_KEYS:
+    for k in keys:
         try:
             hdr[k] = int(d[k])
         except (TypeError, ValueError):
             raise ValueError("%s: key '%s' is not an integer (%r)" % (path, k, d[k]))
-        if hdr[k] < (0 if k == "num_layers" else 1):
+        if hdr[k] < (0 if k in zero_ok else 1):
             raise ValueError("%s: key '%s' is %d" % (path, k, hdr[k]))
     sd = d["model_state_dict"]
     if not hasattr(sd, "keys"):
         raise ValueError("%s: key 'model_state_dict' is a %s, not a dict" % (path, type(sd).__name__))
+    return hdr, sd
+
+
+def state_array(path, sd, name, want, hdr, conv1d=False):
+    """float32 sd[name], of shape `want`; conv1d also takes a Conv1d weight of kernel size 1, [out, in, 1]"""
+    if name not in sd:
+        raise ValueError("%s: model_state_dict has no key '%s'" % (path, name))
+    t = sd[name]
+    a = t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+    if conv1d and a.ndim == 3 and a.shape[2] == 1:
+        a = a[:, :, 0]
+    if tuple(a.shape) != want:
+        raise ValueError("%s: '%s' has shape %s where the header (%s) needs %s"
+                         % (path, name, tuple(a.shape), ", ".join("%s %d" % kv for kv in hdr.items()), want))
+    return np.ascontiguousarray(a, dtype=np.float32)
+
+
+def load_feedforward_checkpoint(path: str) -> FeedforwardCheckpoint:
+    """torch.load of the dict the reference's trainers save: feature_dim, num_frames, num_layers, hidden_dim,
+    num_classes and model_state_dict with layers.{i}.weight / layers.{i}.bias, i = 0 .. num_layers.  Every shape is
+    checked against the header; the errors name the key."""
+    hdr, sd = open_checkpoint(path, HEADER_KEYS, zero_ok=("num_layers",))
     ins = [hdr["feature_dim"] * hdr["num_frames"]] + [hdr["hidden_dim"]] * hdr["num_layers"]
     outs = [hdr["hidden_dim"]] * hdr["num_layers"] + [hdr["num_classes"]]
-    ws, bs = [], []
-    for i, (k_in, k_out) in enumerate(zip(ins, outs)):
-        for name, want, dst in (("layers.%d.weight" % i, (k_out, k_in), ws), ("layers.%d.bias" % i, (k_out,), bs)):
-            if name not in sd:
-                raise ValueError("%s: model_state_dict has no key '%s'" % (path, name))
-            t = sd[name]
-            a = t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
-            if tuple(a.shape) != want:
-                raise ValueError("%s: '%s' has shape %s where the header (feature_dim %d x num_frames %d, num_layers %d,"
-                                 " hidden_dim %d, num_classes %d) needs %s"
-                                 % (path, name, tuple(a.shape), hdr["feature_dim"], hdr["num_frames"],
-                                    hdr["num_layers"], hdr["hidden_dim"], hdr["num_classes"], want))
-            dst.append(np.ascontiguousarray(a, dtype=np.float32))
+    ws = [state_array(path, sd, "layers.%d.weight" % i, (n, k), hdr) for i, (k, n) in enumerate(zip(ins, outs))]
+    bs = [state_array(path, sd, "layers.%d.bias" % i, (n,), hdr) for i, n in enumerate(outs)]
     extra = [k for k in sd.keys() if k.startswith("layers.") and k.split(".")[1].isdigit()
              and int(k.split(".")[1]) > hdr["num_layers"]]
     if extra:
@@ -202,15 +230,14 @@ def load_feedforward_checkpoint(path: str) -> FeedforwardCheckpoint:
 
 @dataclass
 class EgsConfig:
-    feat_type: Optional[str]    # None (raw), "cmvn" or "pca"
+    feat_type: Optional[str]    # None (raw), "cmvn" or "pca"; "cmvn_utt" too from load_rnn_egs_config
     feat_path: Optional[str]    # the stats file / the transform matrix
     left: int
     right: int
 
 
-def load_egs_config(path: str) -> EgsConfig:
-    """The pickled dict {'feat_type': 'cmvn,<path>' | 'pca,<path>' | None, 'concat_feats': 'L,R' | None} that
-    data_prep_feedforward.py:132-135 writes."""
+def read_egs_config(path: str, need=("feat_type", "concat_feats")):
+    """(d, left, right): the pickled dict of egs.config, holding the keys of `need`, and its concat_feats 'L,R'"""
     try:
         with open(path, "rb") as f:
             d = pickle.load(f)
@@ -220,16 +247,9 @@ def load_egs_config(path: str) -> EgsConfig:
         raise ValueError("%s: not a pickled egs.config (%s)" % (path, e))
     if not isinstance(d, dict):
         raise ValueError("%s: egs.config is a %s, not a dict" % (path, type(d).__name__))
-    for k in ("feat_type", "concat_feats"):
+    for k in need:
         if k not in d:
             raise ValueError("%s: egs.config has no key '%s'" % (path, k))
-    ft, fp = None, None
-    if d["feat_type"]:
-        if not isinstance(d["feat_type"], str) or d["feat_type"].count(",") < 1:
-            raise ValueError("%s: 'feat_type' must be '<cmvn|pca>,<path>' or None, got %r" % (path, d["feat_type"]))
-        ft, fp = d["feat_type"].split(",", 1)
-        if ft not in ("cmvn", "pca") or not fp:
-            raise ValueError("%s: 'feat_type' must be '<cmvn|pca>,<path>' or None, got %r" % (path, d["feat_type"]))
     left = right = 0
     if d["concat_feats"]:
         try:
@@ -239,6 +259,20 @@ def load_egs_config(path: str) -> EgsConfig:
                 raise ValueError
         except (AttributeError, IndexError, ValueError):
             raise ValueError("%s: 'concat_feats' must be '<left>,<right>' or None, got %r" % (path, d["concat_feats"]))
+    return d, left, right
+
+
+def load_egs_config(path: str) -> EgsConfig:
+    """The pickled dict {'feat_type': 'cmvn,<path>' | 'pca,<path>' | None, 'concat_feats': 'L,R' | None} that
+    data_prep_feedforward.py:132-135 writes.  Any other feat_type is refused."""
+    d, left, right = read_egs_config(path)
+    ft, fp = None, None
+    if d["feat_type"]:
+        if not isinstance(d["feat_type"], str) or d["feat_type"].count(",") < 1:
+            raise ValueError("%s: 'feat_type' must be '<cmvn|pca>,<path>' or None, got %r" % (path, d["feat_type"]))
+        ft, fp = d["feat_type"].split(",", 1)
+        if ft not in ("cmvn", "pca") or not fp:
+            raise ValueError("%s: 'feat_type' must be '<cmvn|pca>,<path>' or None, got %r" % (path, d["feat_type"]))
     return EgsConfig(ft, fp, left, right)
 
 
@@ -255,15 +289,21 @@ def round_ark(v: np.ndarray, decimals: int) -> np.ndarray:
 # ---------------------------------------------------------------------------------------------
 # runner: MatReader -> pinned double-buffered staging -> one NnetPlan.compute per batch -> writer
 # ---------------------------------------------------------------------------------------------
-class NnetRunner:
-    """PostRunner's two slots around a network plan.  `pca,<mat>` runs a stand-alone XformPlan first (the
-    reference transforms before it splices), then the network plan with the splice only."""
+class NnetRunner(SlotRunner):
+    """post.py's two slots around a model plan.  `pca,<mat>` runs a stand-alone XformPlan first (the reference
+    transforms before it splices), then the model plan with the splice only.  A tool differs (RnnRunner, rnn.py) in
+    the class attributes, in _new_plan and in the hooks _admit, _added and _norm_args."""
+    NORM_VARS = False                   # the apply-cmvn --norm-vars the tool's command line implies
+    FEAT_TYPES = ("cmvn", "pca")        # egs.feat_type values that are not raw features
+    BATCH_ROWS, PROG = 16384, "extract-posterior"
 
-    def __init__(self, ckpt: FeedforwardCheckpoint, egs: EgsConfig, layer: int = 0, mode: str = "raw", prior=None,
-                 prior_weight: float = 0.8, device: int = 0, batch_rows: int = 16384, decimals: int = 3,
-                 prog: str = "extract-posterior", log=None):
+    def __init__(self, ckpt, egs: EgsConfig, layer: int = 0, mode: str = "raw", prior=None, prior_weight: float = 0.8,
+                 device: int = 0, batch_rows: Optional[int] = None, decimals: int = 3, prog: Optional[str] = None,
+                 log=None):
+        prog = prog or self.PROG
         self.ckpt, self.egs, self.layer, self.mode = ckpt, egs, int(layer), mode
-        self.device, self.batch_rows, self.decimals = int(device), max(1, int(batch_rows)), int(decimals)
+        self.device, self.decimals = int(device), int(decimals)
+        self.batch_rows = max(1, int(self.BATCH_ROWS if batch_rows is None else batch_rows))
         self.prior_weight = float(prior_weight)
         self.log = log or (lambda m: print("WARNING (%s) %s" % (prog, m), file=sys.stderr))
         if egs.left + egs.right + 1 != ckpt.num_frames:
@@ -271,15 +311,18 @@ class NnetRunner:
                              % (ckpt.num_frames, egs.left, egs.right))
         if not 0 <= self.layer <= ckpt.num_layers:
             raise ValueError("--layer %d: the model has %d hidden layers" % (self.layer, ckpt.num_layers))
-        self.norm_host = self.pca_host = None
-        if egs.feat_type == "cmvn":
+        self.norm_host = self.pca_host = self.utt_stats = None
+        feat_type = egs.feat_type if egs.feat_type in self.FEAT_TYPES else None
+        if feat_type == "cmvn":
             st = read_kaldi_dmatrix(egs.feat_path)
             if st.shape != (2, ckpt.feature_dim + 1):
                 raise ValueError("%s: CMVN stats of shape %s for a model of feature dimension %d (need 2 x %d)"
                                  % (egs.feat_path, " x ".join(str(v) for v in st.shape), ckpt.feature_dim,
                                     ckpt.feature_dim + 1))
-            self.norm_host = cmvn_norm(st, norm_means=True, norm_vars=False)
-        elif egs.feat_type == "pca":
+            self.norm_host = cmvn_norm(st, norm_means=True, norm_vars=self.NORM_VARS)
+        elif feat_type == "cmvn_utt":
+            self.utt_stats = dict(read_dmatrix_table("scp:" + egs.feat_path))
+        elif feat_type == "pca":
             m = read_kaldi_matrix(egs.feat_path)
             if m.shape[0] != ckpt.feature_dim:
                 raise ValueError("%s: a transform to %d columns for a model of feature dimension %d"
@@ -294,11 +337,14 @@ class NnetRunner:
         self.dim, self.plan, self.pre, self.slots = None, None, None, None
         self.num_done = self.num_err = 0
 
+    def _new_plan(self, cfg, rows):
+        return NnetPlan(cfg, self.ckpt.weights, self.ckpt.biases, max_rows=rows, device=self.device)
+
     def _make_plan(self, rows):
         cfg = PostConfig(dim=self.ckpt.feature_dim, left_context=self.egs.left, right_context=self.egs.right)
         if self.plan is not None:
             self.plan.close()
-        self.plan = NnetPlan(cfg, self.ckpt.weights, self.ckpt.biases, max_rows=rows, device=self.device)
+        self.plan = self._new_plan(cfg, rows)
 
     def _setup(self, dim):
         self.dim = dim
@@ -325,71 +371,31 @@ class NnetRunner:
                     if self.pre is not None else None)
         return sl
 
+    def _norm_args(self, sl):
+        """hook: (norm, norm_index) of slot sl's batch"""
+        return self.norm, None
+
     def _launch(self, sl):
         n = sl.fill
         d_in = sl.d_in[:n]
         d_in.copy_(sl.h_in[:n], non_blocking=True)
         if self.pre is not None:
             d_in = self.pre.compute(d_in, sl.lens, self.pca, out=sl.d_mid)[:n]
-        self.plan.compute(d_in, sl.lens, norm=self.norm, norm_vars=False, tap=self.layer, mode=self.mode,
-                          prior=self.prior, prior_weight=self.prior_weight, out=sl.d_out)
+        norm, idx = self._norm_args(sl)
+        self.plan.compute(d_in, sl.lens, norm=norm, norm_index=idx, norm_vars=self.NORM_VARS, tap=self.layer,
+                          mode=self.mode, prior=self.prior, prior_weight=self.prior_weight, out=sl.d_out)
         sl.h_out[:n].copy_(sl.d_out[:n], non_blocking=True)
         sl.done = torch.cuda.Event()
         sl.done.record()
 
-    def _drain(self, sl, writer):
-        if sl.done is None:
-            return
-        sl.done.synchronize()
-        host = round_ark(sl.h_out.numpy()[:sl.fill], self.decimals)
-        pos = 0
-        for k, n in zip(sl.keys, sl.lens):
-            writer.write(k, host[pos:pos + n])
-            pos += n
-            self.num_done += 1
-        sl.keys, sl.lens, sl.fill, sl.done = [], [], 0, None
+    def _host(self, v):
+        return round_ark(v, self.decimals)
 
-    def _admit(self, utt):
-        """hook: False skips the utterance (the hook has logged and counted it); anything else goes to _added"""
-        return None
-
-    def _added(self, sl, extra):
-        """hook: the utterance _admit returned `extra` for has been appended to slot sl"""
-
-    def run(self, rspecifier: str, writer: FeatWriter):
-        cur = 0
-        for utt, m in MatReader(rspecifier):
-            if self.dim is None and m.shape[0] > 0:
-                self._setup(m.shape[1])
-            if m.shape[0] == 0 or m.shape[1] != self.dim:
-                self.log("Empty or mismatched feature matrix for utterance %s (%d x %d)" % (utt, m.shape[0], m.shape[1]))
-                self.num_err += 1
-                continue
-            extra = self._admit(utt)
-            if extra is False:
-                continue
-            sl = self.slots[cur]
-            if sl.fill and sl.fill + m.shape[0] > sl.rows:
-                self._launch(sl)
-                cur ^= 1
-                sl = self.slots[cur]
-                self._drain(sl, writer)   # the batch before the one just launched
-            if m.shape[0] > sl.rows:      # one utterance longer than a batch: the slot and the plan grow to hold it
-                self._drain(sl, writer)
-                self._drain(self.slots[cur ^ 1], writer)   # the old plan's workspaces are still being read
-                self._make_plan(m.shape[0])
-                self.slots[cur] = sl = self._slot(m.shape[0])
-            sl.h_in[sl.fill:sl.fill + m.shape[0]].numpy()[...] = m
-            sl.fill += m.shape[0]
-            sl.keys.append(utt)
-            sl.lens.append(m.shape[0])
-            self._added(sl, extra)
-        if self.slots:
-            if self.slots[cur].fill:
-                self._launch(self.slots[cur])
-            self._drain(self.slots[cur ^ 1], writer)
-            self._drain(self.slots[cur], writer)
-        return self.num_done, self.num_err
+    def _grow(self, cur, rows):
+        self._drain(self.slots[cur])
+        self._drain(self.slots[cur ^ 1])   # the old plan's workspaces are still being read
+        self._make_plan(rows)
+        self.slots[cur] = self._slot(rows)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -425,21 +431,12 @@ def _load_prior(path):
         raise ValueError("%s: not a pickled prior vector (%s)" % (path, e))
 
 
-def main_extract_posterior(argv=None):
-    prog = "extract-posterior"
-    a = extract_posterior_parser().parse_args(argv)
+def run_model_tool(prog, a, make_runner, did):
+    """What extract-posterior and dump-genclassifier-outputs do with their parsed arguments `a` (scp, save_file):
+    make_runner() loads the files and returns the runner; `did` opens the final LOG line.  Returns the exit status."""
     writer = None
     try:
-        ckpt = load_feedforward_checkpoint(a.model)
-        egs = load_egs_config(a.egs_config)
-        mode, prior = "raw", None
-        if a.layer == 0:           # as in the reference, the options of layer 0 are ignored for a hidden layer
-            if a.prior:
-                mode, prior = "loglike", _load_prior(a.prior)
-            elif a.add_softmax:
-                mode = "softmax"
-        runner = NnetRunner(ckpt, egs, layer=a.layer, mode=mode, prior=prior, prior_weight=a.prior_weight,
-                            device=a.device, batch_rows=a.batch_rows, decimals=a.ark_precision, prog=prog)
+        runner = make_runner()
         rspec = a.scp if _split_specifier(a.scp)[0] else "scp:" + a.scp
         if _split_specifier(a.save_file)[0]:
             wspec = a.save_file
@@ -458,8 +455,27 @@ def main_extract_posterior(argv=None):
             writer.abort()
         raise
     writer.close()
-    print("LOG (%s) Extracted posteriors for %d utterances, errors on %d" % (prog, done, err), file=sys.stderr)
+    print("LOG (%s) %s for %d utterances, errors on %d" % (prog, did, done, err), file=sys.stderr)
     return 0 if done else 1
+
+
+def main_extract_posterior(argv=None):
+    prog = "extract-posterior"
+    a = extract_posterior_parser().parse_args(argv)
+
+    def make_runner():
+        ckpt = load_feedforward_checkpoint(a.model)
+        egs = load_egs_config(a.egs_config)
+        mode, prior = "raw", None
+        if a.layer == 0:           # as in the reference, the options of layer 0 are ignored for a hidden layer
+            if a.prior:
+                mode, prior = "loglike", _load_prior(a.prior)
+            elif a.add_softmax:
+                mode = "softmax"
+        return NnetRunner(ckpt, egs, layer=a.layer, mode=mode, prior=prior, prior_weight=a.prior_weight,
+                          device=a.device, batch_rows=a.batch_rows, decimals=a.ark_precision, prog=prog)
+
+    return run_model_tool(prog, a, make_runner, "Extracted posteriors")
 
 
 if __name__ == "__main__":

@@ -393,6 +393,10 @@ class _Slot:
         self.d_out = torch.empty((rows, out_dim), dtype=torch.float32, device=dev)
         self.h_out = torch.empty((rows, out_dim), dtype=torch.float32, pin_memory=True)
         self.rows = rows
+        self.reset()
+
+    def reset(self):
+        """empty, for the next batch"""
         self.keys, self.lens, self.norm_idx, self.norms = [], [], [], []
         self.where = {}  # stats key -> row of this batch's norm table
         self.mat_idx, self.mats, self.mwhere = [], [], {}  # the same for the transform table
@@ -400,7 +404,74 @@ class _Slot:
         self.done = None
 
 
-class PostRunner:
+class SlotRunner:
+    """The two-slot loop of every table-to-table tool: while the device works on one slot's batch, the host fills
+    the other and writes out the batch before.  A subclass sets dim, slots (None until _setup or _admit has made
+    them), num_done, num_err and log, and provides
+      _setup(dim)       called with the width of the first non-empty matrix
+      _admit(utt)       False skips the utterance (the hook has logged and counted it); anything else goes to _added
+      _added(sl, extra) the utterance _admit returned `extra` for has been appended to slot sl
+      _launch(sl)       copy in, compute, copy out, record sl.done
+      _grow(cur, rows)  replace slots[cur] by one of `rows` rows for an utterance longer than a slot
+      _host(v)          what is written for the device's rows v of a batch (the identity here)"""
+
+    def _admit(self, utt):
+        return None
+
+    def _added(self, sl, extra):
+        pass
+
+    def _host(self, v):
+        return v
+
+    def _drain(self, sl):
+        if sl.done is None:
+            return
+        sl.done.synchronize()
+        host = self._host(sl.h_out.numpy()[:sl.fill])
+        pos = 0
+        for k, n in zip(sl.keys, sl.lens):
+            self.writer.write(k, host[pos:pos + n])
+            pos += n
+            self.num_done += 1
+        sl.reset()
+
+    def run(self, rspecifier: str, writer: "FeatWriter"):
+        self.writer = writer
+        cur = 0
+        for utt, m in MatReader(rspecifier):
+            if self.dim is None and m.shape[0] > 0:
+                self._setup(m.shape[1])
+            if m.shape[0] == 0 or m.shape[1] != self.dim:
+                self.log("Empty or mismatched feature matrix for utterance %s (%d x %d)" % (utt, m.shape[0], m.shape[1]))
+                self.num_err += 1
+                continue
+            extra = self._admit(utt)
+            if extra is False:
+                continue
+            sl = self.slots[cur]
+            if sl.fill and sl.fill + m.shape[0] > sl.rows:
+                self._launch(sl)
+                cur ^= 1
+                sl = self.slots[cur]
+                self._drain(sl)           # the batch before the one just launched
+            if m.shape[0] > sl.rows:      # one utterance longer than a batch: the slot grows to hold it
+                self._grow(cur, m.shape[0])
+                sl = self.slots[cur]
+            sl.h_in[sl.fill:sl.fill + m.shape[0]].numpy()[...] = m
+            sl.fill += m.shape[0]
+            sl.keys.append(utt)
+            sl.lens.append(m.shape[0])
+            self._added(sl, extra)
+        if self.slots:
+            if self.slots[cur].fill:
+                self._launch(self.slots[cur])
+            self._drain(self.slots[cur ^ 1])
+            self._drain(self.slots[cur])
+        return self.num_done, self.num_err
+
+
+class PostRunner(SlotRunner):
     """opts: the PostConfig fields but dim (taken from the first matrix); stats: None, a [2, D+1] matrix (global)
     or a dict key -> matrix with utt2spk (None: looked up by the utterance id).  transform: None, one [N, C] matrix
     (global) or a dict key -> matrix looked up like the stats (the same utt2spk); the plan is made from the first
@@ -500,77 +571,45 @@ class PostRunner:
         sl.done = torch.cuda.Event()
         sl.done.record()
 
-    def _drain(self, sl, writer):
-        if sl.done is None:
-            return
-        sl.done.synchronize()
-        host = sl.h_out.numpy()
-        pos = 0
-        for k, n in zip(sl.keys, sl.lens):
-            writer.write(k, host[pos:pos + n])
-            pos += n
-            self.num_done += 1
-        sl.keys, sl.lens, sl.norm_idx, sl.norms, sl.where, sl.fill, sl.done = [], [], [], [], {}, 0, None
-        sl.mat_idx, sl.mats, sl.mwhere = [], [], {}
-
-    def run(self, rspecifier: str, writer: FeatWriter):
-        cur = 0
-        for utt, m in MatReader(rspecifier):
-            if self.dim is None and m.shape[0] > 0:
-                self._setup(m.shape[1])
-            if m.shape[0] == 0 or m.shape[1] != self.dim:
-                self.log("Empty or mismatched feature matrix for utterance %s (%d x %d)" % (utt, m.shape[0], m.shape[1]))
+    def _admit(self, utt):
+        nv = mv = None
+        if self.apply_norm:
+            nv = self._norm_for(utt)
+            if nv is None:
+                self.log("No normalization statistics available for key %s, producing no output for this "
+                         "utterance" % utt)
                 self.num_err += 1
-                continue
-            nv = None
-            if self.apply_norm:
-                nv = self._norm_for(utt)
-                if nv is None:
-                    self.log("No normalization statistics available for key %s, producing no output for this "
-                             "utterance" % utt)
-                    self.num_err += 1
-                    continue
-            mv = None
-            if self.transform is not None:
-                mv = self._mat_for(utt)
-                if mv is None:
-                    self.num_err += 1
-                    continue
-                if self.plan is None:
-                    N, C = mv[1].shape
-                    self._make_plan(XformPlan(PostConfig(dim=self.dim, **self.opts), N, C == self.in_dim + 1,
-                                              self.device))
-            sl = self.slots[cur]
-            if sl.fill and sl.fill + m.shape[0] > sl.rows:
-                self._launch(sl)
-                cur ^= 1
-                sl = self.slots[cur]
-                self._drain(sl, writer)   # the batch before the one just launched
-            if m.shape[0] > sl.rows:      # one utterance longer than a batch: the slot grows to hold it
-                self._drain(sl, writer)
-                self.slots[cur] = sl = _Slot(m.shape[0], self.dim, self.plan.out_dim, sl.d_in.device)
-            sl.h_in[sl.fill:sl.fill + m.shape[0]].numpy()[...] = m
-            sl.fill += m.shape[0]
-            sl.keys.append(utt)
-            sl.lens.append(m.shape[0])
-            if nv is not None:
-                key, vec = nv
-                if key not in sl.where:
-                    sl.where[key] = len(sl.norms)
-                    sl.norms.append(vec)
-                sl.norm_idx.append(sl.where[key])
-            if mv is not None:
-                key, mat = mv
-                if key not in sl.mwhere:
-                    sl.mwhere[key] = len(sl.mats)
-                    sl.mats.append(mat)
-                sl.mat_idx.append(sl.mwhere[key])
-        if self.slots:
-            if self.slots[cur].fill:
-                self._launch(self.slots[cur])
-            self._drain(self.slots[cur ^ 1], writer)
-            self._drain(self.slots[cur], writer)
-        return self.num_done, self.num_err
+                return False
+        if self.transform is not None:
+            mv = self._mat_for(utt)
+            if mv is None:
+                self.num_err += 1
+                return False
+            if self.plan is None:
+                N, C = mv[1].shape
+                self._make_plan(XformPlan(PostConfig(dim=self.dim, **self.opts), N, C == self.in_dim + 1,
+                                          self.device))
+        return nv, mv
+
+    def _added(self, sl, extra):
+        nv, mv = extra
+        if nv is not None:
+            key, vec = nv
+            if key not in sl.where:
+                sl.where[key] = len(sl.norms)
+                sl.norms.append(vec)
+            sl.norm_idx.append(sl.where[key])
+        if mv is not None:
+            key, mat = mv
+            if key not in sl.mwhere:
+                sl.mwhere[key] = len(sl.mats)
+                sl.mats.append(mat)
+            sl.mat_idx.append(sl.mwhere[key])
+
+    def _grow(self, cur, rows):
+        sl = self.slots[cur]
+        self._drain(sl)
+        self.slots[cur] = _Slot(rows, self.dim, self.plan.out_dim, sl.d_in.device)
 
 
 # ---------------------------------------------------------------------------------------------

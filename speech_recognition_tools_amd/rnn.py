@@ -19,11 +19,14 @@ pseudo log-likelihoods latgen-faster-mapped consumes.
   * --ae_type=vae samples its latent and --ae_type=vaeenc loads a path hard-coded in the reference: neither is
     reproduced, both exit 1 with a message.  --add_softmax uses the max-subtracted form nnet.py documents.
 Out of scope: training, and the CURL, multimod and CNN models.
+
+The plan's compute, the runner, the file readers and the command line's body are nnet.py's (StagePlan, NnetRunner,
+open_checkpoint, read_egs_config, run_model_tool); this module adds the stage list, the GRU checkpoints, the
+per-utterance stats and --override_trans.
 """
 import argparse
 import ctypes
 import os
-import pickle
 import sys
 from dataclasses import dataclass, field
 from typing import List, Optional, Sequence, Tuple
@@ -33,21 +36,21 @@ import torch
 
 from . import _lib
 from ._lib import FdlpRnnConfigC, check, lib, ptr
-from .cmvn import read_kaldi_dmatrix
-from .nnet import MODES, EgsConfig, NnetRunner, _load_prior
-from .post import (FeatWriter, PostConfig, _make_batch, _split_specifier, cmvn_norm, read_dmatrix_table,
-                   read_kaldi_matrix)
+from .nnet import (EgsConfig, NnetRunner, StagePlan, _load_prior, open_checkpoint, read_egs_config, run_model_tool,
+                   state_array)
+from .post import PostConfig, cmvn_norm
 
 KINDS = {"gru": _lib.FDLP_RNN_GRU, "linear": _lib.FDLP_RNN_LINEAR, "linear_relu": _lib.FDLP_RNN_LINEAR_RELU}
 KIND_NAMES = {v: k for k, v in KINDS.items()}
 
 
-class RnnPlan:
+class RnnPlan(StagePlan):
     """cmvn | deltas | splice | a list of stages.  stages[s] is ("gru", w_ih [3H, K], w_hh [3H, H], b_ih [3H],
     b_hh [3H]) in nn.GRU's layout (gate order r, z, n), or ("linear" | "linear_relu", w [N, K], b [N]); the ReLU of
     "linear_relu" is applied when the next stage loads the output, so tapping it gives the pre-activation.
     device=-1 gives a host-only plan (dims, workspace_bytes, group_utts, lds_bytes, groups()); it needs the shapes
     only: pass stages=None with `kinds` and `dims` (dims[0] the row width the stages of cfg give)."""
+    _DESTROY, _COMPUTE = "fdlp_rnn_plan_destroy", "fdlp_rnn_compute"
 
     def __init__(self, cfg: PostConfig, stages, max_rows: int = 131072, max_utts: Optional[int] = None,
                  device: int = 0, kinds: Optional[Sequence] = None, dims: Optional[Sequence[int]] = None):
@@ -113,21 +116,6 @@ class RnnPlan:
         self.out_dim = self.dims[-1]
         self.workspace_bytes, self.group_utts, self.lds_bytes = wsb.value, gu.value, lds.value
 
-    def close(self):
-        h = getattr(self, "_h", None)
-        if h and lib is not None:
-            lib.fdlp_rnn_plan_destroy(h)
-            self._h = None
-
-    def __del__(self):
-        self.close()
-
-    def tap_dim(self, tap: int) -> int:
-        """columns of the output for `tap` (0: the last stage; s: stage n_stages - 1 - s)"""
-        if not 0 <= tap < self.n_stages:
-            raise ValueError("tap %d is outside 0 .. %d (the model has %d stages)" % (tap, self.n_stages - 1, self.n_stages))
-        return self.dims[self.n_stages - tap]
-
     def groups(self, lengths: Sequence[int]) -> Tuple[np.ndarray, np.ndarray, int]:
         """(group_of, slot_of, n_groups) of a batch with these lengths: the table gru_scan_kernel is launched with"""
         lens = np.ascontiguousarray(np.asarray(lengths, dtype=np.int32))
@@ -145,29 +133,6 @@ class RnnPlan:
         ms = (ctypes.c_double * 2)()
         check(lib.fdlp_rnn_times(self._h, ms))
         return ms[0], ms[1]
-
-    def compute(self, feats: torch.Tensor, lengths: Sequence[int], norm: Optional[torch.Tensor] = None,
-                norm_index: Optional[Sequence[int]] = None, norm_vars: bool = True, tap: int = 0, mode: str = "raw",
-                prior: Optional[torch.Tensor] = None, prior_weight: float = 0.8,
-                offsets: Optional[Sequence[int]] = None, out: Optional[torch.Tensor] = None, stream=None) -> torch.Tensor:
-        """As NnetPlan.compute.  tap 0: the last stage's output, in `mode` raw, softmax or loglike; tap s > 0: the
-        output of stage n_stages - 1 - s, raw.  Returns out [rows, tap_dim(tap)]."""
-        if mode not in MODES:
-            raise ValueError("mode must be one of %s" % ", ".join(MODES))
-        b, out, keep = _make_batch("RnnPlan.compute", self.cfg.dim, self.tap_dim(tap), feats, lengths, norm,
-                                   norm_index, norm_vars, offsets, out)
-        pp = None
-        if mode == "loglike":
-            if (not isinstance(prior, torch.Tensor) or prior.dtype != torch.float32 or prior.device != feats.device
-                    or tuple(prior.shape) != (self.out_dim,)):
-                raise ValueError("RnnPlan.compute: loglike needs prior, a float32 [%d] tensor on the features' device"
-                                 % self.out_dim)
-            prior = prior.contiguous()
-            pp = ctypes.c_void_p(prior.data_ptr())
-        s = stream if stream is not None else torch.cuda.current_stream(feats.device)
-        check(lib.fdlp_rnn_compute(self._h, ctypes.byref(b), int(tap), MODES[mode], pp, float(prior_weight),
-                                   ctypes.c_void_p(s.cuda_stream)))
-        return out
 
 
 # ---------------------------------------------------------------------------------------------
@@ -196,16 +161,7 @@ NORMAL_KEYS = ("feature_dim", "num_frames", "num_classes", "encoder_num_layers",
 
 
 def _state_array(path, sd, name, want, hdr):
-    if name not in sd:
-        raise ValueError("%s: model_state_dict has no key '%s'" % (path, name))
-    t = sd[name]
-    a = t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
-    if a.ndim == 3 and a.shape[2] == 1:   # a Conv1d of kernel size 1: [out, in, 1]
-        a = a[:, :, 0]
-    if tuple(a.shape) != want:
-        raise ValueError("%s: '%s' has shape %s where the header (%s) needs %s"
-                         % (path, name, tuple(a.shape), ", ".join("%s %d" % kv for kv in hdr.items()), want))
-    return np.ascontiguousarray(a, dtype=np.float32)
+    return state_array(path, sd, name, want, hdr, conv1d=True)   # the regression layers are Conv1d of kernel size 1
 
 
 def _gru_stages(path, sd, prefix, n, k_in, H, hdr):
@@ -232,29 +188,8 @@ def load_rnn_checkpoint(path: str, ae_type: str = "normal") -> RnnCheckpoint:
     the key."""
     if ae_type not in ("noae", "normal"):
         raise ValueError("ae_type %r: only 'noae' and 'normal' models are supported" % (ae_type,))
-    with open(path, "rb"):   # a missing or unreadable file is an OSError that names it
-        pass
-    try:
-        d = torch.load(path, map_location="cpu")
-    except Exception as e:  # an unpickling error of any kind; a truncated archive surfaces as an OSError without a name
-        raise ValueError("%s: not a torch checkpoint (%s)" % (path, e))
-    if not isinstance(d, dict):
-        raise ValueError("%s: the checkpoint is a %s, not a dict" % (path, type(d).__name__))
-    keys = NOAE_KEYS if ae_type == "noae" else NORMAL_KEYS
-    for k in keys + ("model_state_dict",):
-        if k not in d:
-            raise ValueError("%s: the checkpoint has no key '%s' (--ae_type=%s)" % (path, k, ae_type))
-    hdr = {}
-    for k in keys:
-        try:
-            hdr[k] = int(d[k])
-        except (TypeError, ValueError):
-            raise ValueError("%s: key '%s' is not an integer (%r)" % (path, k, d[k]))
-        if hdr[k] < (0 if k == "ae_num_layers" else 1):
-            raise ValueError("%s: key '%s' is %d" % (path, k, hdr[k]))
-    sd = d["model_state_dict"]
-    if not hasattr(sd, "keys"):
-        raise ValueError("%s: key 'model_state_dict' is a %s, not a dict" % (path, type(sd).__name__))
+    hdr, sd = open_checkpoint(path, NOAE_KEYS if ae_type == "noae" else NORMAL_KEYS, zero_ok=("ae_num_layers",),
+                              hint=" (--ae_type=%s)" % ae_type)
     K0, H, C = hdr["feature_dim"] * hdr["num_frames"], hdr["hidden_dim"], hdr["num_classes"]
     if ae_type == "noae":
         stages = _gru_stages(path, sd, "layers", hdr["num_layers"], K0, H, hdr)
@@ -274,15 +209,8 @@ def load_rnn_checkpoint(path: str, ae_type: str = "normal") -> RnnCheckpoint:
 def load_rnn_egs_config(path: str, override_trans: Optional[str] = None) -> EgsConfig:
     """egs.config as dump_genclassifier_outputs.py:68-91 reads it: feat_type '<type>,<path>' with type pca, cmvn or
     cmvn_utt (anything else, None included, is raw), replaced by --override_trans when given; concat_feats 'L,R'."""
-    try:
-        with open(path, "rb") as f:
-            d = pickle.load(f)
-    except (OSError, IOError):
-        raise
-    except Exception as e:
-        raise ValueError("%s: not a pickled egs.config (%s)" % (path, e))
-    if not isinstance(d, dict) or "concat_feats" not in d or (override_trans is None and "feat_type" not in d):
-        raise ValueError("%s: egs.config must be a dict with the keys 'feat_type' and 'concat_feats'" % path)
+    d, left, right = read_egs_config(path, ("feat_type", "concat_feats") if override_trans is None
+                                     else ("concat_feats",))
     spec = override_trans if override_trans is not None else d["feat_type"]
     ft = fp = None
     if isinstance(spec, str) and spec.split(",")[0] in ("pca", "cmvn", "cmvn_utt"):
@@ -290,62 +218,19 @@ def load_rnn_egs_config(path: str, override_trans: Optional[str] = None) -> EgsC
         fp = fp.split(",")[0]
         if not fp:
             raise ValueError("%s: '%s' names no file" % ("--override_trans" if override_trans is not None else path, spec))
-    left = right = 0
-    if d["concat_feats"]:
-        try:
-            t = d["concat_feats"].split(",")
-            left, right = int(t[0]), int(t[1])
-            if len(t) != 2 or left < 0 or right < 0:
-                raise ValueError
-        except (AttributeError, IndexError, ValueError):
-            raise ValueError("%s: 'concat_feats' must be '<left>,<right>' or None, got %r" % (path, d["concat_feats"]))
     return EgsConfig(ft, fp, left, right)
 
 
 # ---------------------------------------------------------------------------------------------
-# runner: NnetRunner's two pinned slots around an RnnPlan; whole utterances, --norm-vars=true
+# runner: NnetRunner around an RnnPlan; whole utterances, --norm-vars=true, per-utterance stats as a norm table
 # ---------------------------------------------------------------------------------------------
 class RnnRunner(NnetRunner):
-    def __init__(self, ckpt: RnnCheckpoint, egs: EgsConfig, mode: str = "raw", prior=None, prior_weight: float = 0.8,
-                 device: int = 0, batch_rows: int = 131072, decimals: int = 3, prog: str = "dump-genclassifier-outputs",
-                 log=None):
-        self.ckpt, self.egs, self.layer, self.mode = ckpt, egs, 0, mode
-        self.device, self.batch_rows, self.decimals = int(device), max(1, int(batch_rows)), int(decimals)
-        self.prior_weight = float(prior_weight)
-        self.log = log or (lambda m: print("WARNING (%s) %s" % (prog, m), file=sys.stderr))
-        if egs.left + egs.right + 1 != ckpt.num_frames:
-            raise ValueError("the model was trained on %d spliced frames but egs.config splices -%d..+%d"
-                             % (ckpt.num_frames, egs.left, egs.right))
-        self.norm_host = self.pca_host = self.utt_stats = None
-        want = (2, ckpt.feature_dim + 1)
-        if egs.feat_type == "cmvn":
-            st = read_kaldi_dmatrix(egs.feat_path)
-            if st.shape != want:
-                raise ValueError("%s: CMVN stats of shape %s for a model of feature dimension %d (need 2 x %d)"
-                                 % (egs.feat_path, " x ".join(str(v) for v in st.shape), ckpt.feature_dim, want[1]))
-            self.norm_host = cmvn_norm(st, norm_means=True, norm_vars=True)
-        elif egs.feat_type == "cmvn_utt":
-            self.utt_stats = dict(read_dmatrix_table("scp:" + egs.feat_path))
-        elif egs.feat_type == "pca":
-            m = read_kaldi_matrix(egs.feat_path)
-            if m.shape[0] != ckpt.feature_dim:
-                raise ValueError("%s: a transform to %d columns for a model of feature dimension %d"
-                                 % (egs.feat_path, m.shape[0], ckpt.feature_dim))
-            self.pca_host = m
-        self.prior_host = None
-        if mode == "loglike":
-            p = np.ascontiguousarray(prior, dtype=np.float32).reshape(-1)
-            if p.shape[0] != ckpt.num_classes:
-                raise ValueError("the prior has %d entries for %d classes" % (p.shape[0], ckpt.num_classes))
-            self.prior_host = p
-        self.dim, self.plan, self.pre, self.slots = None, None, None, None
-        self.num_done = self.num_err = 0
+    NORM_VARS = True
+    FEAT_TYPES = ("cmvn", "cmvn_utt", "pca")
+    BATCH_ROWS, PROG = 131072, "dump-genclassifier-outputs"
 
-    def _make_plan(self, rows):
-        cfg = PostConfig(dim=self.ckpt.feature_dim, left_context=self.egs.left, right_context=self.egs.right)
-        if self.plan is not None:
-            self.plan.close()
-        self.plan = RnnPlan(cfg, self.ckpt.stages, max_rows=rows, max_utts=rows, device=self.device)
+    def _new_plan(self, cfg, rows):
+        return RnnPlan(cfg, self.ckpt.stages, max_rows=rows, max_utts=rows, device=self.device)
 
     def _admit(self, utt):
         if self.utt_stats is None:
@@ -362,25 +247,10 @@ class RnnRunner(NnetRunner):
         if extra is not None:
             sl.norms.append(extra)
 
-    def _launch(self, sl):
-        n = sl.fill
-        d_in = sl.d_in[:n]
-        d_in.copy_(sl.h_in[:n], non_blocking=True)
-        if self.pre is not None:
-            d_in = self.pre.compute(d_in, sl.lens, self.pca, out=sl.d_mid)[:n]
-        norm, idx = self.norm, None
-        if self.utt_stats is not None:
-            norm, idx = torch.from_numpy(np.stack(sl.norms)).to(d_in.device), list(range(len(sl.norms)))
-        self.plan.compute(d_in, sl.lens, norm=norm, norm_index=idx, norm_vars=True, tap=0, mode=self.mode,
-                          prior=self.prior, prior_weight=self.prior_weight, out=sl.d_out)
-        sl.h_out[:n].copy_(sl.d_out[:n], non_blocking=True)
-        sl.done = torch.cuda.Event()
-        sl.done.record()
-
-    def _drain(self, sl, writer):
-        if sl.done is not None:
-            super()._drain(sl, writer)
-            sl.norms = []
+    def _norm_args(self, sl):
+        if self.utt_stats is None:
+            return self.norm, None
+        return torch.from_numpy(np.stack(sl.norms)).to(sl.d_in.device), list(range(len(sl.norms)))
 
 
 # ---------------------------------------------------------------------------------------------
@@ -416,8 +286,8 @@ def main_dump_genclassifier_outputs(argv=None):
         print("ERROR (%s) --ae_type=%s is not supported%s" % (prog, a.ae_type, ": %s" % why if why else ""),
               file=sys.stderr)
         return 1
-    writer = None
-    try:
+
+    def make_runner():
         ckpt = load_rnn_checkpoint(a.model, a.ae_type)
         egs = load_rnn_egs_config(a.egs_config, a.override_trans)
         mode, prior = "raw", None
@@ -425,28 +295,10 @@ def main_dump_genclassifier_outputs(argv=None):
             mode, prior = "loglike", _load_prior(a.prior)
         elif a.add_softmax:
             mode = "softmax"
-        runner = RnnRunner(ckpt, egs, mode=mode, prior=prior, prior_weight=a.prior_weight, device=a.device,
-                           batch_rows=a.batch_rows, decimals=a.ark_precision, prog=prog)
-        rspec = a.scp if _split_specifier(a.scp)[0] else "scp:" + a.scp
-        if _split_specifier(a.save_file)[0]:
-            wspec = a.save_file
-        else:
-            base = os.path.abspath(a.save_file)
-            wspec = "ark,scp:%s.ark,%s.scp" % (base, base)
-        writer = FeatWriter(wspec)
-        done, err = runner.run(rspec, writer)
-    except (OSError, ValueError, _lib.FdlpError) as e:
-        if writer is not None:
-            writer.abort()
-        print("ERROR (%s) %s" % (prog, e), file=sys.stderr)
-        return 1
-    except BaseException:
-        if writer is not None:
-            writer.abort()
-        raise
-    writer.close()
-    print("LOG (%s) Dumped outputs for %d utterances, errors on %d" % (prog, done, err), file=sys.stderr)
-    return 0 if done else 1
+        return RnnRunner(ckpt, egs, mode=mode, prior=prior, prior_weight=a.prior_weight, device=a.device,
+                         batch_rows=a.batch_rows, decimals=a.ark_precision, prog=prog)
+
+    return run_model_tool(prog, a, make_runner, "Dumped outputs")
 
 
 if __name__ == "__main__":

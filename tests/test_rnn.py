@@ -276,6 +276,25 @@ def test_host_only_plan_info_and_refusals():
     RnnPlan(cfg, None, max_rows=10, device=-1, kinds=["gru", "linear"], dims=[117, 384, 3])
 
 
+FF_KINDS = ["linear_relu", "linear_relu", "linear"]                    # a feed-forward net as stages
+
+
+def test_feedforward_net_is_the_linear_only_stage_plan():
+    """one plan behind both fronts: the same shapes, and workspaces that differ by the group table alone"""
+    from speech_recognition_tools_amd.nnet import NnetPlan
+    from speech_recognition_tools_amd.post import PostConfig
+    from speech_recognition_tools_amd.rnn import RnnPlan
+    cfg, dims = PostConfig(dim=13, left_context=4, right_context=4), [117, 70, 9, 5]
+    for max_rows, max_utts in ((1000, 70), (7, 1), (33, GU), (33, GU + 1)):
+        a = NnetPlan(cfg, None, None, max_rows=max_rows, device=-1, dims=dims)
+        b = RnnPlan(cfg, None, max_rows=max_rows, max_utts=max_utts, device=-1, kinds=FF_KINDS, dims=dims)
+        assert a.dims == b.dims == dims and a.n_linear == b.n_stages == 3 and b.kinds == FF_KINDS
+        assert [a.tap_dim(t) for t in range(3)] == [b.tap_dim(t) for t in range(3)] == [5, 9, 70]
+        assert a.workspace_bytes == 2 * 4 * max_rows * 70
+        assert b.workspace_bytes - a.workspace_bytes == 16 * GU * -(-max_utts // GU)
+        assert b.lds_bytes == 0                                         # no scan
+
+
 def test_group_table():
     from speech_recognition_tools_amd._lib import FDLP_E_INVALID, FdlpError
     from speech_recognition_tools_amd.post import PostConfig
@@ -557,6 +576,35 @@ def test_gpu_epilogues_and_refusals():
     assert e.value.code == FDLP_E_INVALID and "utterance 1" in str(e.value)
     torch.cuda.synchronize()
     assert_bits_equal(run_rnn(plan, xs), logits, "after the refusals")
+
+
+@pytest.mark.gpu
+def test_gpu_feedforward_net_through_both_fronts_is_bit_identical():
+    """the same network as an NnetPlan and as the stages linear_relu, linear_relu, linear of an RnnPlan: K_0 = 20,
+    widths 70, 9, 5 (three layers, so both workspaces and the ReLU flag; N on both sides of 64), utterances of 1, 37
+    and 130 rows (more than one 128-row tile, the last partial) with NaN rows between them.  Every tap raw, and tap 0
+    in softmax and in loglike with a random prior, bit for bit."""
+    from speech_recognition_tools_amd.nnet import NnetPlan
+    from speech_recognition_tools_amd.post import PostConfig
+    from speech_recognition_tools_amd.rnn import RnnPlan
+    rng = np.random.default_rng(11)
+    cfg = PostConfig(dim=5, left_context=1, right_context=2)
+    ws, bs = TN_.make_net(rng, [20, 70, 9, 5])
+    lens, offsets, n_rows = [1, 37, 130], [2, 5, 45], 180
+    xs = [ark_like(rng, T, 5, 2.0 * (i % 2)) for i, T in enumerate(lens)]
+    norms, idx = two_norms(xs)
+    prior = np.log(rng.dirichlet(np.ones(5))).astype(np.float32)
+    nnet = NnetPlan(cfg, ws, bs, max_rows=n_rows)
+    rnn = RnnPlan(cfg, [(k, w, b) for k, w, b in zip(FF_KINDS, ws, bs)], max_rows=n_rows, max_utts=3)
+    assert nnet.dims == rnn.dims == [20, 70, 9, 5]
+    cases = [dict(tap=t) for t in range(3)] + [dict(mode="softmax"), dict(mode="loglike", prior=prior, prior_weight=0.3)]
+    for kw in cases:
+        a = TN_.run_nnet(nnet, xs, norms, idx, offsets=offsets, n_rows=n_rows, **dict(kw))
+        b = TN_.run_nnet(rnn, xs, norms, idx, offsets=offsets, n_rows=n_rows, **dict(kw))
+        assert a.shape == b.shape == (n_rows, nnet.tap_dim(kw.get("tap", 0)))
+        for o, T in zip(offsets, lens):
+            assert np.all(np.isfinite(a[o:o + T])), kw
+            assert_bits_equal(a[o:o + T], b[o:o + T], "%s rows %d..%d" % (sorted(kw), o, o + T))
 
 
 CHECKS_CHILD = r"""
