@@ -71,7 +71,9 @@ def complex_cepstrum(a, gg, lim):
 
 def modspec_complex_features(signal, nfilters=15, coeff_0=5, coeff_n=30, order=50, fduration=0.5, frate=100,
                              fbank_type="mel,1", keep_even=False, no_window=False, compensate_noise=False,
-                             absolute_value=False, srate=16000):
+                             absolute_value=False, srate=16000, y_hook=None):
+    """y_hook(y, s) -> y, when given, replaces each band's autocorrelation before the LPC (the tests measure the
+    chain's response to a rounding-sized change of y with it)."""
     import scipy.linalg as _sla
     N = int(srate * fduration)
     L = int(fduration * srate / 2)
@@ -89,6 +91,8 @@ def modspec_complex_features(signal, nfilters=15, coeff_0=5, coeff_n=30, order=5
             s = fb[j, 0:-1] * X[i, :]
             S = np.fft.fft(s, len(s))
             y = np.fft.ifft(S * np.conj(S))
+            if y_hook is not None:
+                y = y_hook(y, s)
             a = np.append(1, _sla.solve_toeplitz(y[0:order], -y[1:order + 1]))
             gg = y[0] + np.sum(a * y[1:order + 2])
             mod = complex_cepstrum(a, gg, coeff_n)

@@ -397,8 +397,9 @@ __global__ __launch_bounds__(256) void mel_kernel(MelConsts c, const MelFrame* _
           if (pcm_kind == 0) {
             sv = (double)((const int16_t*)pcm)[fd.pcm_off + t];
             if (fd.noise_off >= 0) sv = __dadd_rn(sv, __dmul_rn(fd.alpha, (double)noise[fd.noise_off + t]));
-          } else if (pcm_kind == 1) {
+          } else if (pcm_kind == 1) {  // float64 values of another WAV dtype: sig + alp*ns as for int16
             sv = ((const double*)pcm)[fd.pcm_off + t];
+            if (fd.noise_off >= 0) sv = __dadd_rn(sv, __dmul_rn(fd.alpha, (double)noise[fd.noise_off + t]));
           } else {  // convolve(int16 s, diff kernel, 'same') -> int64 (computeMelSpectrum.py:136-139)
             const int16_t* x = (const int16_t*)pcm + fd.pcm_off;
             long long acc = 0;

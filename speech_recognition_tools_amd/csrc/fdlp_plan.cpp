@@ -2534,9 +2534,10 @@ int fdlp_nnet_compute(fdlp_nnet_plan* p, const fdlp_post_batch* b, int32_t tap, 
 int fdlp_reverb(const fdlp_reverb_batch* b, void* stream) {
   if (!b || b->n_utt < 0 || !b->pcm_off || !b->utt_len || !b->rir_dev || b->rir_len < 1 || !b->out_dev ||
       !b->out_len || (b->n_utt > 0 && !b->pcm_dev) || (b->noise_dev && (!b->noise_off || !b->noise_alpha)) ||
-      (b->pcm_kind != FDLP_PCM_I16 && b->pcm_kind != FDLP_PCM_F64) ||
-      (b->pcm_kind == FDLP_PCM_F64 && (b->noise_dev || b->preprocess != FDLP_PRE_NONE)))
+      (b->pcm_kind != FDLP_PCM_I16 && b->pcm_kind != FDLP_PCM_F64))
     return fail(FDLP_E_INVALID, "fdlp_reverb: bad args");
+  if (b->pcm_kind == FDLP_PCM_F64 && (b->noise_dev || b->preprocess != FDLP_PRE_NONE))
+    return fail(FDLP_E_INVALID, "fdlp_reverb: noise mixing and diff preprocessing need int16 PCM (float64 PCM is taken as it is)");
   if (b->n_utt == 0) return FDLP_OK;
   hipStream_t s = (hipStream_t)stream;
   const int R = b->rir_len;

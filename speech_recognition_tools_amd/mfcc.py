@@ -79,10 +79,11 @@ class MfccPlan:
 
     def compute(self, pcm: torch.Tensor, lengths: Sequence[int], offsets: Optional[Sequence[int]] = None,
                 noise: Optional[torch.Tensor] = None, noise_off=None, noise_alpha=None,
-                ark_decimals: int = 3, want_f64: bool = False, stream=None):
+                ark_decimals: int = 3, want_f64: bool = False, stream=None, preprocess=None):
         """(feats float32 [sum F, width], row offsets [n+1], feats_f64 or None) of a batch on the device.
         pcm holds the WAVs' own sample values (int16, or float64 e.g. from augment.reverb); the 2**-15
-        scaling of the reference happens in the kernel."""
+        scaling of the reference happens in the kernel.  preprocess="diff" is passed on and refused by
+        fdlp_mfcc_compute (computeMfccFeatures.py has no diff option), like the sibling plans' argument."""
         if not pcm.is_cuda:
             raise ValueError("pcm must be a device tensor")
         if pcm.dtype not in (torch.int16, torch.float64):
@@ -122,7 +123,9 @@ class MfccPlan:
         b.out_dev, b.out_row = out.data_ptr(), ptr(rows_c, ctypes.c_int64)
         b.out_f64_dev = out64.data_ptr() if out64 is not None else None
         b.ark_decimals = int(ark_decimals)
-        b.preprocess = _lib.FDLP_PRE_NONE
+        if preprocess not in (None, "diff"):
+            raise ValueError("preprocess must be None or 'diff'")
+        b.preprocess = _lib.FDLP_PRE_DIFF if preprocess == "diff" else _lib.FDLP_PRE_NONE
         s = stream if stream is not None else torch.cuda.current_stream(pcm.device)
         check(lib.fdlp_mfcc_compute(self._h, ctypes.byref(b), ctypes.c_void_p(s.cuda_stream)))
         return out, rows, out64

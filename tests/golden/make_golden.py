@@ -206,8 +206,9 @@ def cli_options_fixture():
     print("wrote cli_options.json", len(opts))
 
 
-def run_reference_mel(signals, opts, noise_seed=None, noise=None, noise_name=None, rir=None):
-    """computeMelSpectrum.compute_mel_spectrum with get_kaldi_ark captured (copy-feats is absent)."""
+def run_reference_mel(signals, opts, noise_seed=None, noise=None, noise_name=None, rir=None, raw=None):
+    """computeMelSpectrum.compute_mel_spectrum with get_kaldi_ark captured (copy-feats is absent).  raw: {utt:
+    file bytes} written as they are instead of wavfile.write(signals[utt])."""
     sys.path.insert(0, os.path.join(REF, "src/featgen"))
     import computeMelSpectrum as cm  # noqa: E402
     captured = {}
@@ -218,7 +219,11 @@ def run_reference_mel(signals, opts, noise_seed=None, noise=None, noise_name=Non
         with open(scp, "w") as f:
             for utt, x in signals.items():
                 p = os.path.join(td, utt + ".wav")
-                wavfile.write(p, 16000, x)
+                if raw and utt in raw:
+                    with open(p, "wb") as fw:
+                        fw.write(raw[utt])
+                else:
+                    wavfile.write(p, 16000, x)
                 f.write("%s %s\n" % (utt, p))
         if noise is not None:
             os.makedirs(os.path.join(td, "noises"), exist_ok=True)
@@ -447,9 +452,95 @@ def wav_kinds_fixtures():
     save("wav_kinds_diff", sig, opts, 78, run_reference(sig, opts, 78, raw=raw), more=more)
 
 
+SIBLING_COMPLEX = OrderedDict([
+    # set -> options over MODSPEC_DEFAULT with nfilters=4, coeff_0/coeff_n/order: the trip counts of the
+    # 64-lane loops of cplx_autocorr_kernel / cplx_lpc_out_kernel (parity section)
+    ("modspec_complex_o65", dict(order=65, coeff_0=1, coeff_n=66)),   # 67 lags; Durbin's last step still 64 values
+    ("modspec_complex_o66", dict(order=66, coeff_0=1, coeff_n=67)),   # step k = 66: the first lane with two values
+    ("modspec_complex_o130", dict(order=130, coeff_0=3, coeff_n=100)),
+    ("modspec_complex_o236", dict(order=236, coeff_0=1, coeff_n=200, absolute_value=True, keep_even=True,
+                                  compensate_noise=True)),
+    # coeff_0 = 41 keeps the file under 300 KB (coeff_0 = 5 gives 320 KB); the recursion is sequential, so the
+    # stored cepstra 40..299 depend on every earlier one
+    ("modspec_complex_c300", dict(order=40, coeff_0=41, coeff_n=300, absolute_value=True)),
+])
+SIBLING_MEL = OrderedDict([
+    ("mel_trunc256", dict(fduration=0.025, nfft=256)),            # frame (400) longer than nfft: fft truncates
+    ("mel_nfft600_odd", dict(fduration=0.0251, nfft=600)),        # L = 401 (odd), nfft/2 = 2.2.3.5.5
+    ("mel_nfft4096", dict(nfft=4096, nfilters=40, spectrum_type="power")),  # 128 KiB of LDS
+])
+
+
+def sibling_edge_fixtures():
+    """Short-signal fixtures at the sizes where the sibling kernels (fdlp_misc.hip: cplx_autocorr_kernel,
+    cplx_lpc_out_kernel, mel_kernel) take paths the older goldens never run: complex modulation with
+    order + 2 > 64 lags, more than one Durbin value per lane and coeff_n > order + 1; mel frames longer than
+    nfft, an odd frame with nfft/2 = 300, nfft = 4096; and noise mixing on non-16-bit WAVs (float32, 8-bit
+    unsigned, 24-bit) through computeMelSpectrum.py."""
+    import io
+    sig = OrderedDict()
+    sig["e1"] = speech_like(2500, 101)
+    sig["e2"] = speech_like(1000, 102)
+    sig["ewhite"] = white(1700, 103)
+    for name, over in SIBLING_COMPLEX.items():
+        opts = dict(MODSPEC_DEFAULT, nfilters=4, complex_modulation=True, **over)
+        save(name, sig, opts, 0, run_reference_modspec(sig, opts))
+    sig = OrderedDict()
+    sig["n1"] = speech_like(3000, 111)
+    sig["nshort"] = speech_like(300, 112)      # shorter than one frame: reflect padding on both sides
+    sig["nwhite"] = white(1000, 113)
+    for name, over in SIBLING_MEL.items():
+        opts = dict(MEL_DEFAULT, **over)
+        save(name, sig, opts, 0, run_reference_mel(sig, opts))
+    # the same three signals as the dtypes scipy returns for float32, 8-bit and 24-bit WAVs; the reference squares
+    # each in its own dtype (features.py:24-31), so the integer ones are chosen with a positive wrapped mean
+    kin, raw = OrderedDict(), {}
+    kin["kf32"] = (sig["n1"].astype(np.float64) / 32768.0).astype(np.float32)
+    kin["ku8"] = np.clip(sig["nshort"].astype(np.int64) // 64 + 128, 0, 255).astype(np.uint8)
+    seed = 113
+    while True:  # a quiet 24-bit signal: at full scale the wrapped energies give an alpha too small to see
+        v24 = np.clip(white(1000, seed).astype(np.int64) * 3, -(2 ** 23), 2 ** 23 - 1)
+        if np.mean((v24 << 8).astype(np.int32) ** 2) > 0:
+            break
+        seed += 100
+    raw["ki24"] = wav24_bytes(v24)
+    kin["ki24"] = wavfile.read(io.BytesIO(raw["ki24"]))[1]
+    assert kin["ki24"].dtype == np.int32 and np.array_equal(kin["ki24"], (v24 << 8).astype(np.int32))
+    for u, x in kin.items():
+        if u not in raw:
+            b = io.BytesIO()
+            wavfile.write(b, 16000, x)
+            raw[u] = b.getvalue()
+        assert wavfile.read(io.BytesIO(raw[u]))[1].dtype == x.dtype
+    noise = white(16000, 114, scale=1000.0)
+    noise_seed = 9
+    while True:  # the reference's own alpha of every utterance must be finite (no wrapped negative mean energy)
+        rs, alphas = np.random.RandomState(noise_seed), []
+        for x in kin.values():
+            off = int(np.floor(rs.rand() * (len(noise) - len(x))))
+            ns = noise[off:off + len(x)]
+            with np.errstate(invalid="ignore", divide="ignore"):
+                alphas.append(np.sqrt(np.mean(x ** 2) / (np.mean(ns ** 2) * (10 ** (10 / 10)))))
+        if np.all(np.isfinite(alphas)) and np.all(np.array(alphas) > 0):
+            break
+        noise_seed += 1
+    opts = dict(MEL_DEFAULT, add_noise="babble,10")
+    feats = run_reference_mel(kin, opts, noise_seed=noise_seed, noise=noise, noise_name="babble", raw=raw)
+    assert all(np.isfinite(feats[u]).all() for u in kin)
+    clean = run_reference_mel(kin, MEL_DEFAULT, raw=raw)  # the mixing must show in every utterance's features
+    assert all(np.abs(feats[u] - clean[u]).max() > 0.01 for u in kin), \
+        {u: float(np.abs(feats[u] - clean[u]).max()) for u in kin}
+    more ={"wav_" + u: np.frombuffer(raw[u], dtype=np.uint8) for u in kin}
+    save("mel_kinds_noise", kin, opts, 0, feats, extra=dict(noise_seed=noise_seed),
+         more=dict(more, noise_babble=noise))
+
+
 def main():
     os.environ.setdefault("PYTHONDONTWRITEBYTECODE", "1")
     sys.dont_write_bytecode = True
+    if "--sibling-edges-only" in sys.argv:
+        sibling_edge_fixtures()
+        return
     if "--wav-kinds-only" in sys.argv:
         wav_kinds_fixtures()
         return

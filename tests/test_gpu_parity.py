@@ -469,3 +469,221 @@ def test_features_into_pinned_host_memory_match_device_output():
     np.testing.assert_array_equal(host.numpy(), dev_out.cpu().numpy())
     with pytest.raises(ValueError):
         plan.compute(pcm, lens, jit, out=torch.empty(tuple(dev_out.shape), dtype=torch.float32))
+
+
+# ---------------------------------------------------------------------------------------------------------
+# addReverb edges: ties of the cross-correlation maximum and outputs shorter than the input
+# ---------------------------------------------------------------------------------------------------------
+def _tie_rir(last_peak):
+    """Equal peaks at 5 and 5 + 256 (one thread's scan of rev_select_kernel, 256 apart) and `last_peak` at
+    5 + 1024 (the second rev_xcorr_kernel block), and a smaller tap after each so the aligned output is not all zero."""
+    rir = np.zeros(1300)
+    rir[[5, 5 + 256]] = 0.5
+    rir[5 + 1024] = last_peak
+    rir[[300, 1100]] = 0.125
+    return rir
+
+
+def _impulse(T, a=1000):
+    x = np.zeros(T, dtype=np.int16)
+    x[0] = a
+    return x
+
+
+REVERB_EDGES = {
+    # name: (signal, rir, output length); with x = a delta_0 the correlation at shift s is a^2 rir[s], products of
+    # powers of two and 1000: exact in fp64, so equal peaks tie on the device as they do in numpy
+    "tie_across_blocks": (_impulse(400), _tie_rir(0.5), 400),       # largest tied shift 1029 wins
+    "tie_in_one_thread": (_impulse(400), _tie_rir(0.25), 400),      # 5 and 261 tie, 261 wins
+    "all_zero": (np.zeros(300, dtype=np.int16), _tie_rir(0.5), 299),  # every shift ties: sh* = R - 1
+    "rir_of_one_tap": (np.arange(-250, 250).astype(np.int16), np.array([0.5]), 499),
+    "one_sample_long_rir": (_impulse(1, 1234), np.cos(np.arange(1300.0)) * np.exp(-np.arange(1300.0) / 200), 1),
+    "one_sample_one_tap": (_impulse(1, 77), np.array([0.75]), 0),
+}
+
+
+@pytest.mark.parametrize("case", sorted(REVERB_EDGES))
+def test_reverb_edges_vs_oracle(case):
+    """rev_select_kernel keeps the LARGEST shift attaining the maximum (numpy's first argmax over the reversed
+    correlation) through its strided scan, its LDS tree and the shifts of the second rev_xcorr_kernel block, and
+    the output is one sample short when that shift is the last one: lengths and samples against O.add_reverb.
+    The empty output of a one-sample utterance under a one-tap RIR is then refused by the plan."""
+    from oracle import fdlp_oracle as O
+    from speech_recognition_tools_amd import FdlpError, FdlpPlan, FeatureConfig
+    from speech_recognition_tools_amd.augment import reverb
+    x, rir, want_len = REVERB_EDGES[case]
+    ref = O.add_reverb(x, rir)
+    assert ref.size == want_len, (case, ref.size)
+    # a neighbour on either side: the edge utterance is neither the first nor the last of the batch
+    pad = np.arange(1, 600, dtype=np.int16)
+    lens = [pad.size, x.size, pad.size]
+    pcm = torch.from_numpy(np.concatenate([pad, x, pad])).cuda()
+    out, ol = reverb(pcm, lens, torch.from_numpy(rir).cuda())
+    assert [int(v) for v in ol] == [O.add_reverb(pad, rir).size, want_len, O.add_reverb(pad, rir).size]
+    got = out.cpu().numpy()[pad.size:pad.size + want_len]
+    assert got.shape == ref.shape
+    if want_len:
+        assert np.abs(got - ref).max() <= 1e-9 * max(1.0, np.abs(ref).max())
+        if case.startswith("tie"):
+            assert np.abs(ref).max() > 0
+            np.testing.assert_array_equal(got, ref)  # exact products: the device's samples are numpy's
+    else:  # the batch as augment.reverb hands it on: the emptied utterance between its two neighbours
+        plan = FdlpPlan(FeatureConfig(), device=0, max_frames=16)
+        with pytest.raises(FdlpError, match="too short"):
+            plan.compute(out, [int(v) for v in ol], None, offsets=[0, pad.size, pad.size + x.size])
+
+
+# ---------------------------------------------------------------------------------------------------------
+# input kinds: every entry point x PCM kind x preprocessing either matches its oracle or says why not
+# ---------------------------------------------------------------------------------------------------------
+KIND_ENTRIES = ("spectrogram", "modspec", "modspec_complex", "mel", "mfcc", "reverb")
+KIND_PCM = ("int16", "float64")
+KIND_PRE = ("none", "noise", "diff")
+# (entry, kind, pre) -> what the FdlpError has to say.  float64 PCM is the sample values of a non-16-bit WAV (or a
+# reverberated signal); mel's diff filter, the MFCC script's own noise mixing and fdlp_reverb's preprocessing are
+# written for int16 samples only, and computeMfccFeatures.py has no diff option at all (so no oracle either).
+KIND_REFUSED = {
+    ("mel", "float64", "diff"): "int16",
+    ("mfcc", "float64", "noise"): "int16",
+    ("mfcc", "int16", "diff"): "no diff",
+    ("mfcc", "float64", "diff"): "no diff",
+    ("reverb", "float64", "noise"): "int16",
+    ("reverb", "float64", "diff"): "int16",
+}
+KIND_SNR, KIND_SEED, KIND_NOISE_SEED = 10.0, 4, 6
+KIND_FDLP = dict(nfilters=5, order=20, fduration=0.5, frate=100, fbank_type="mel,1")
+_KIND_DATA = {}
+
+
+def _kind_data():
+    if not _KIND_DATA:
+        rng = np.random.default_rng(77)
+        t = np.arange(9000) / 16000.0
+        tone = 2500 * np.sin(2 * np.pi * 310 * t) * (1 + 0.5 * np.sin(2 * np.pi * 4 * t))
+        sig = []
+        for T, base, amp in ((9000, tone, 300), (5003, 0.0, 1500)):
+            while True:  # the reference squares int16 in int16 (features.py:24-31): keep a positive wrapped mean
+                s = np.round(base + amp * rng.standard_normal(T)).astype(np.int16)
+                if np.mean(s ** 2) > 1.0:
+                    break
+            sig.append(s)
+        _KIND_DATA["sig"] = sig
+        _KIND_DATA["noise"] = np.round(rng.standard_normal(12000) * 60).astype(np.int16)  # squares stay in int16
+        _KIND_DATA["rir"] = np.concatenate([[0.8], rng.standard_normal(299) * np.exp(-np.arange(299) / 60.0) * 0.2])
+    return _KIND_DATA["sig"], _KIND_DATA["noise"], _KIND_DATA["rir"]
+
+
+def _kind_cell(entry, kind, pre):
+    """(device call -> list of fp64 outputs per utterance, oracle outputs, error bound per output) of one cell."""
+    import random
+    from oracle import fdlp_oracle as O
+    from oracle import mel_oracle as MO
+    from oracle import modspec_oracle as MS
+    from speech_recognition_tools_amd import FdlpPlan, FeatureConfig, NpRandom, PyRandom
+    from speech_recognition_tools_amd.augment import noise_params, noise_params_f64, reverb
+    from speech_recognition_tools_amd.melspec import MelConfig, MelPlan
+    from speech_recognition_tools_amd.mfcc import MfccConfig, MfccPlan
+    sigs, noise, rir = _kind_data()
+    xs = [s.astype(np.float64) if kind == "float64" else s for s in sigs]   # what the caller holds
+    lens = [x.size for x in xs]
+    nr = NpRandom(KIND_NOISE_SEED)
+    draws = [nr.rand() for _ in xs]
+    assert draws == list(np.random.RandomState(KIND_NOISE_SEED).rand(len(xs)))
+    # host side: the reference's preprocessing of each signal in its own dtype
+    if entry == "mfcc":  # computeMfccFeatures.py: / 2**15 first, its own add_noise_to_wav on the float64 arrays
+        params = [noise_params_f64(x, noise, KIND_SNR, u) for x, u in zip(xs, draws)]
+        pres = [x / np.power(2, 15) + (a * (noise[o:o + x.size] / np.power(2, 15)) if pre == "noise" else 0.0)
+                for x, (o, a) in zip(xs, params)]
+    else:
+        params = [noise_params(x, noise, KIND_SNR, u) for x, u in zip(xs, draws)]
+        pres = [O.diff_signal(x) if pre == "diff" else O.add_noise(x, noise, KIND_SNR, u) if pre == "noise" else x
+                for x, u in zip(xs, draws)]
+        if pre == "noise":
+            for x, u, (o, a) in zip(xs, draws, params):  # the device's (offset, alpha) are the oracle's
+                ro, ra = O.noise_mix_params(x, noise, KIND_SNR, u)
+                assert o == ro and a == float(ra)
+    assert all(np.isfinite(a) and a > 0 for _, a in params)
+    kw = {}
+    if pre == "diff":
+        kw = dict(preprocess="diff")
+    elif pre == "noise":
+        kw = dict(noise=torch.from_numpy(noise).cuda(), noise_off=[o for o, _ in params],
+                  noise_alpha=[a for _, a in params])
+    pcm = torch.from_numpy(np.concatenate(xs)).cuda()
+
+    def split(out64, rows):
+        out64 = out64.cpu().numpy()
+        return [out64[rows[i]:rows[i + 1]] for i in range(len(xs))]
+
+    if entry in ("spectrogram", "modspec", "modspec_complex"):
+        if entry == "spectrogram":
+            cfg = FeatureConfig(coeff_num=20, coeff_range="1,20", overlap_fraction=0.25, **KIND_FDLP)
+            orc = O.FdlpOracle(O.FdlpConfig(coeff_num=20, coeff_range="1,20", overlap_fraction=0.25, **KIND_FDLP))
+            prng = random.Random(KIND_SEED)
+            want = [orc.utterance(x, prng) for x in pres]
+            bound = [TOL * np.ones_like(w) for w in want]                         # this module's bar
+        else:
+            cfg = FeatureConfig(mode=entry, window="hanning", coeff_num=20, coeff_0=2, **KIND_FDLP)
+            f = MS.modspec_features if entry == "modspec" else MS.modspec_complex_features
+            want = [f(np.asarray(x, dtype=np.float64), coeff_0=2, coeff_n=20, **KIND_FDLP) for x in pres]
+            bound = [1e-7 * np.maximum(1.0, np.abs(w)) for w in want]             # tests/test_modspec.py TOL
+        plan = FdlpPlan(cfg, device=0, max_frames=128)
+
+        def run():
+            jit = PyRandom(KIND_SEED).randbits2(sum(max(plan.geometry(T)[0] - 1, 0) for T in lens))
+            _, rows, out64 = plan.compute(pcm, lens, jit, want_f64=True, **kw)
+            return split(out64, rows)
+    elif entry == "mel":
+        plan = MelPlan(MelConfig(), device=0, max_frames=128)
+        want = [MO.mel_spectrum(x) for x in pres]
+        bound = [1e-9 * np.maximum(1.0, np.abs(w)) for w in want]                 # tests/test_melspec.py
+
+        def run():
+            _, rows, out64 = plan.compute(pcm, lens, want_f64=True, **kw)
+            return split(out64, rows)
+    elif entry == "mfcc":
+        plan = MfccPlan(MfccConfig(), device=0, max_frames=128)
+        t = plan.tables()
+        K, nb, nbp = t["K"], t["nb"], t["nbpad"]
+        want = []
+        for x in pres:  # the reference chain on the plan's tables (tests/test_mfcc.py holds them to the reference)
+            fr = MO.get_frames(x, 16000, 100, 0.02)[:, :K]
+            mag = np.hypot(fr @ t["tw"][:K, :nb], fr @ t["tw"][:K, nbp:nbp + nb])
+            want.append(np.log10(mag @ t["fold"].T) @ t["dct"])
+        bound = [1e-6 * np.ones_like(w) for w in want]                            # tests/test_mfcc.py
+
+        def run():
+            _, rows, out64 = plan.compute(pcm, lens, want_f64=True, **kw)
+            return split(out64, rows)
+    else:
+        want = [O.add_reverb(x, rir) for x in pres]
+        bound = [1e-9 * max(1.0, np.abs(w).max()) * np.ones_like(w) for w in want]  # test_reverb_kernel_vs_oracle
+
+        def run():
+            out, ol = reverb(pcm, lens, torch.from_numpy(rir).cuda(), **kw)
+            out = out.cpu().numpy()
+            offs = np.concatenate([[0], np.cumsum(lens)[:-1]])
+            return [out[o:o + n] for o, n in zip(offs, ol)]
+    return run, want, bound
+
+
+@pytest.mark.parametrize("pre", KIND_PRE)
+@pytest.mark.parametrize("kind", KIND_PCM)
+@pytest.mark.parametrize("entry", KIND_ENTRIES)
+def test_input_kind_table(entry, kind, pre):
+    """Every (entry point, PCM kind, preprocessing) cell computes its oracle's features at that entry's own bar,
+    or raises FdlpError naming the cause; KIND_REFUSED lists the refusals, and nothing is computed silently
+    without its preprocessing (mel float64 + noise did: mel_kernel ignored the noise for float64 PCM)."""
+    from speech_recognition_tools_amd import FdlpError
+    assert set(KIND_REFUSED) <= {(e, k, p) for e in KIND_ENTRIES for k in KIND_PCM for p in KIND_PRE}
+    run, want, bound = _kind_cell(entry, kind, pre)
+    assert all(np.isfinite(w).all() and w.size for w in want)
+    if (entry, kind, pre) in KIND_REFUSED:
+        with pytest.raises(FdlpError, match=KIND_REFUSED[(entry, kind, pre)]):
+            run()
+        return
+    got = run()
+    for i, (g, w, b) in enumerate(zip(got, want, bound)):
+        assert g.shape == w.shape, (entry, kind, pre, i, g.shape, w.shape)
+        excess = np.abs(g - w) / b
+        assert excess.max() <= 1.0, (entry, kind, pre, i, float(np.abs(g - w).max()))
