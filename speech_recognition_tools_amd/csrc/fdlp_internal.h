@@ -255,6 +255,7 @@ hipError_t launch_mfcc(const MfccConsts& c, const MfccFrame* frames, int nframes
                        const int16_t* noise, double* cep, float* out, double* out64, int decimals, hipStream_t s);
 size_t mfcc_lds_bytes(int rt, int Kpad, int nbpad, int nfilters);
 int mfcc_row_tiles(int Kpad, int nbpad, int nfilters);  // 16-frame row tiles per workgroup (2, 1; 0 = too large)
+hipError_t checks_mfcc(unsigned int* v, bool reset);
 
 // Post-processing chain (apply-cmvn | add-deltas | splice-feats, fdlp_post.hip): one tile of consecutive
 // frames of one utterance and the plan constants.

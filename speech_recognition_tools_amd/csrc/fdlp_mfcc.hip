@@ -69,10 +69,12 @@ __global__ __launch_bounds__(256) void mfcc_kernel(MfccConsts c, const MfccFrame
     const bool live = f < nframes;
     MfccFrame fd{};
     if (live) fd = frames[f];
+    FDLP_CHECK(f >= 0 && (!live || (fd.T >= 1 && fd.k >= 0 && fd.k < fd.F)));
     for (int i = lane; i < c.Kpad; i += 64) {
       double v = 0.0;
       if (live && i < c.K && !(FDLP_MFCC_SKIP & 1)) {
         const int64_t t = reflect_idx((int64_t)fd.k * c.hop + i - c.ext, fd.T);
+        FDLP_CHECK(t >= 0 && t < fd.T);
         double sv;
         if (pcm_kind == 0) {
           sv = (double)((const int16_t*)pcm)[fd.pcm_off + t];
@@ -82,6 +84,7 @@ __global__ __launch_bounds__(256) void mfcc_kernel(MfccConsts c, const MfccFrame
         }
         v = __dmul_rn(__dmul_rn(sv, c.window[i]), 0x1p-15);
       }
+      FDLP_CHECK(i < sa && row * sa + i < M * sa);
       A[row * sa + i] = v;
     }
   }
@@ -108,7 +111,9 @@ __global__ __launch_bounds__(256) void mfcc_kernel(MfccConsts c, const MfccFrame
       int ct = wave + 4 * (j0 + j);
       if (ct >= nct) ct = wave + 4 * j0;
       col[j] = 16 * ct + i_lane;
+      FDLP_CHECK(ct >= 0 && ct < nct && c.nbpad + col[j] < tw_ld);
     }
+    FDLP_CHECK(ksteps == 0 || kk_lane < c.Kpad);
     const double* tw = c.tw + (size_t)kk_lane * tw_ld;
     double bc[kMfccNT], bs[kMfccNT], nc[kMfccNT], ns[kMfccNT];
 #pragma unroll
@@ -124,6 +129,7 @@ __global__ __launch_bounds__(256) void mfcc_kernel(MfccConsts c, const MfccFrame
       // step re-reads its own)
       const int adv = st + 1 < ksteps ? 4 : 0;
       const double* twn = tw + (size_t)adv * tw_ld;
+      FDLP_CHECK(4 * st + adv + kk_lane < c.Kpad && (16 * (RT - 1) + i_lane) * sa + 4 * st + adv + kk_lane < M * sa);
 #pragma unroll
       for (int j = 0; j < kMfccNT; ++j) {
         nc[j] = twn[col[j]];
@@ -154,6 +160,7 @@ __global__ __launch_bounds__(256) void mfcc_kernel(MfccConsts c, const MfccFrame
       if (ct < nct) {
         const int k = 16 * ct + i_lane;
         if (k < c.nb) {
+          FDLP_CHECK(k < sm && (16 * (RT - 1) + kk_lane + 12) * sm + k < M * sm);
 #pragma unroll
           for (int r = 0; r < RT; ++r)
 #pragma unroll
@@ -171,7 +178,9 @@ __global__ __launch_bounds__(256) void mfcc_kernel(MfccConsts c, const MfccFrame
     const double* w = c.fold + (size_t)m * c.nb;
     const double* mg = mag + row * sm;
     double acc = 0.0;
+    FDLP_CHECK(0 <= c.lo[m] && c.lo[m] <= c.hi[m] && c.hi[m] <= c.nb && row * sm + c.nb <= M * sm);
     for (int k = c.lo[m]; k < c.hi[m]; ++k) acc = fma(mg[k], w[k], acc);
+    FDLP_CHECK(m < sa && row * sa + m < M * sa);
     mel[row * sa + m] = log10(acc);
   }
   __syncthreads();
@@ -182,12 +191,14 @@ __global__ __launch_bounds__(256) void mfcc_kernel(MfccConsts c, const MfccFrame
     const int f = f0 + row;
     if (f >= nframes) continue;
     const double* ml = mel + row * sa;
+    FDLP_CHECK(row < M && row * sa + c.nfilters <= M * sa);
     double acc = 0.0;
     for (int m = 0; m < c.nfilters; ++m) acc = fma(ml[m], c.dct[m * c.ncep + q], acc);
     if (cep) {  // --context: the splice kernel rounds and stores
       cep[(int64_t)f * c.ncep + q] = acc;
     } else {
       const int64_t o = frames[f].out_row * c.ncep + q;
+      FDLP_CHECK(o >= 0 && o < (int64_t)nframes * c.ncep);  // a batch's output rows are its frames
       if (out64) out64[o] = acc;
       if (out) out[o] = decimals >= 0 ? (float)(nearbyint(acc * scale10) / scale10) : (float)acc;
     }
@@ -210,9 +221,11 @@ __global__ __launch_bounds__(256) void mfcc_splice_kernel(const double* __restri
   if (fd.k < fd.F - C) {
     const int j = col / ncep, q = col % ncep;
     const int src = fd.k + j - C;
+    FDLP_CHECK(!(src >= 0 && src < fd.F) || (g + j - C >= 0 && g + j - C < nframes));
     if (src >= 0 && src < fd.F) v = cep[(int64_t)(g + j - C) * ncep + q];
   }
   const int64_t o = fd.out_row * W + col;
+  FDLP_CHECK(o >= 0 && o < (int64_t)nframes * W);
   if (out64) out64[o] = v;
   if (out) out[o] = decimals >= 0 ? (float)(nearbyint(v * scale10) / scale10) : (float)v;
 }
@@ -243,5 +256,7 @@ hipError_t launch_mfcc(const MfccConsts& c, const MfccFrame* frames, int nframes
   }
   return hipGetLastError();
 }
+
+hipError_t checks_mfcc(unsigned int* v, bool reset) { return fdlp_checks_local(v, reset); }
 
 }  // namespace fdlp

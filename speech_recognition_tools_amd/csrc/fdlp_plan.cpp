@@ -1335,7 +1335,8 @@ int fdlp_set_debug(fdlp_plan* p, int32_t keep_intermediates) {
 int fdlp_device_checks(int32_t* enabled, uint32_t* violations, uint32_t* last_line, int32_t reset) {
   unsigned int tot = 0, line = 0;
   hipError_t (*const fns[])(unsigned int*, bool) = {fdlp::checks_dct, fdlp::checks_autocorr, fdlp::checks_lpc,
-                                                    fdlp::checks_misc, fdlp::checks_post, fdlp::checks_nnet};
+                                                    fdlp::checks_misc, fdlp::checks_post, fdlp::checks_nnet,
+                                                    fdlp::checks_mfcc};
   HIP_TRY(hipDeviceSynchronize());
   for (auto fn : fns) {
     unsigned int v[2] = {0u, 0u};

@@ -8,6 +8,9 @@ src/featgen/computeMfccFeatures.py (extractMelEnergyFeats, with getKaldiArk capt
   mfcc_noise_reverb  --add_noise babble,10 (np.random.seed(7)) --add_reverb small_room, short synthetic RIR;
                      the noise exceeds |181|, so int16-wrapped and float64 energies differ
   cli_options_mfcc.json   the reference's argparse table (:139-150), read from its source with ast
+  mfcc_shape_<row>   the SHAPE_ROWS marked as fixtures (tests/test_mfcc_shapes.py): the tile shapes of mfcc_kernel
+                     that the sets above never reach, each on shape_row_signals(); --shape-edges-only makes these
+  mfcc_shape_ctx7    --nfft 2048 --context 7: F = 8 (one non-zero row), F = 5 <= context, F = 20
 
 Run next to make_golden.py (whose signal helpers it imports):  python tests/golden/make_golden_mfcc.py
 """
@@ -27,6 +30,88 @@ from make_golden import REF, save, speech_like, synthetic_rir, white  # noqa: E4
 
 MFCC_DEFAULT = dict(nfilters=30, fduration=0.02, frate=100, nfft=1024, context=None, add_noise="none",
                     add_reverb=None)
+
+
+# One row per tile shape mfcc_kernel can take (tests/test_mfcc_shapes.py checks that against the plan):
+# (id, options over MFCC_DEFAULT, frames per workgroup the plan picks, whether the reference's output is a fixture)
+SHAPE_ROWS = [
+    ("n1212", dict(nfft=1212), 32, False),                                # the largest two-row-tile shape at K = 320
+    ("n1214", dict(nfft=1214), 16, False),                                # the first one-row-tile shape; 20 col tiles
+    ("n1278", dict(nfft=1278), 16, False),                                # 21 column tiles: a second pass, n even
+    ("n1280", dict(nfft=1280), 16, True),                                 # .. n odd
+    ("n1282", dict(nfft=1282), 16, False),                                # .. n even
+    ("n2048", dict(nfft=2048), 16, True),                                 # 33 column tiles, two passes
+    ("n3000", dict(nfft=3000), 16, True),                                 # 47 column tiles, three passes
+    ("k800", dict(nfft=1600, fduration=0.05, nfilters=64), 16, True),     # K = 800, 13 of 64 cepstra
+    ("tiny", dict(nfft=32, fduration=0.002, nfilters=5), 32, True),       # K = 17, one column tile, L < hop
+    ("widemel", dict(nfft=1024, fduration=0.002, nfilters=40), 32, False),  # nfilters > K
+    ("oddL", dict(nfft=1024, fduration=0.0200625), 32, True),             # L = 321
+    ("n636", dict(nfft=636), 32, False),                                  # n = 319 = L - 1: truncated by one sample
+    ("n638", dict(nfft=638), 32, False),                                  # n = 320 = L
+    ("n640", dict(nfft=640), 32, False),                                  # n = 321 = L + 1: padded by one
+    ("hop533", dict(frate=30), 32, True),                                 # hop > L
+    ("hop128", dict(frate=125), 32, False),
+    ("empty", dict(nfft=64, nfilters=40), 32, True),                      # empty filters: non-finite rows
+]
+SHAPE_CTX = dict(nfft=2048, context=7)
+ONE_FRAME = 5                                                             # samples: shorter than the reflect padding
+# Reflect padding makes a T-sample utterance periodic with period 2 (T - 1).  At n = L = 320 a period of 8 divides
+# the DFT length: the Hamming window's spectrum is then sampled at its near-zeros, the mel energies between the
+# eight lines are 1e-7 of the frame's, and the error bound of their logarithms passes 1e-7 (5.2e-7; the test's
+# cap).  That row's one-frame utterance has 7 samples (period 12) instead.
+ONE_FRAME_OF = {"n638": 7}
+
+
+def shape_row_opts(over):
+    return dict(MFCC_DEFAULT, **over)
+
+
+def n_frames(T, opts, srate=16000):
+    """features.py getFrames (:118-154): the number of frames of T samples."""
+    L, hop = int(srate * opts["fduration"]), int(srate / opts["frate"])
+    lim = T - 1 if L % 2 == 0 else T
+    return 0 if lim <= 0 else (lim - 1) // hop + 1
+
+
+def samples_for(F, opts, srate=16000):
+    """A length of F frames, away from both neighbours."""
+    hop = int(srate / opts["frate"])
+    T = hop * (F - 1) + 2 + min(50, hop // 2)
+    assert n_frames(T, opts) == F
+    return T
+
+
+def shape_row_signals(index):
+    """The four utterances of SHAPE_ROWS[index], of 1, M - 1, M + 1 and 2 frames with M the workgroup's frames:
+    the first two fill one workgroup, the last workgroup has three live rows."""
+    rid, over, M, _ = SHAPE_ROWS[index]
+    opts, seed = shape_row_opts(over), 500 + 10 * index
+    T1 = ONE_FRAME_OF.get(rid, ONE_FRAME)
+    assert n_frames(T1, opts) == 1
+    sig = OrderedDict()
+    sig["s1"] = speech_like(T1, seed)
+    sig["sA"] = speech_like(samples_for(M - 1, opts), seed + 1)
+    sig["sB"] = white(samples_for(M + 1, opts), seed + 2)
+    sig["s2"] = speech_like(samples_for(2, opts), seed + 3)
+    return sig
+
+
+def shape_ctx_signals():
+    opts = shape_row_opts(SHAPE_CTX)
+    sig = OrderedDict()
+    sig["x8"] = speech_like(samples_for(8, opts), 701)      # F = context + 1: one non-zero row
+    sig["x5"] = white(samples_for(5, opts), 702)            # F <= context: every row zero
+    sig["x20"] = speech_like(samples_for(20, opts), 703)
+    return sig
+
+
+def shape_edge_fixtures():
+    for i, (rid, over, _, fixture) in enumerate(SHAPE_ROWS):
+        if fixture:
+            sig, opts = shape_row_signals(i), shape_row_opts(over)
+            save("mfcc_shape_" + rid, sig, opts, 0, run_reference_mfcc(sig, opts))
+    sig, opts = shape_ctx_signals(), shape_row_opts(SHAPE_CTX)
+    save("mfcc_shape_ctx7", sig, opts, 0, run_reference_mfcc(sig, opts))
 
 
 def run_reference_mfcc(signals, opts, noise_seed=None, noise=None, noise_name=None, rir=None):
@@ -82,6 +167,9 @@ def cli_options_fixture():
 
 
 def main():
+    if "--shape-edges-only" in sys.argv:
+        shape_edge_fixtures()
+        return
     sig = OrderedDict()
     sig["c1"] = speech_like(4000, 181)
     sig["c2"] = speech_like(2345, 182)
@@ -118,6 +206,7 @@ def main():
          run_reference_mfcc(sig, opts, noise_seed=7, noise=noise, noise_name="babble", rir=rir),
          extra=dict(noise_seed=7), more={"rir": rir, "noise_babble": noise})
     cli_options_fixture()
+    shape_edge_fixtures()
 
 
 if __name__ == "__main__":

@@ -51,6 +51,9 @@ def test_every_rank_gets_its_pcie_child(gpus):
     res = _run("--gpus", str(gpus), "--utts", "5", "--full", "--dump-outputs", "unused")
     ch = res["xfer_children"]
     assert len(ch) == gpus
+    # the rank's GPU is the rank-th of the visible ones when the caller's environment narrows them
+    vis = os.environ.get("HIP_VISIBLE_DEVICES") or os.environ.get("CUDA_VISIBLE_DEVICES")
+    ids = [v.strip() for v in vis.split(",") if v.strip()] if vis else None
     for r, c in enumerate(ch):
         a = c["argv"]
         assert "--xfer-only" in a and "--dry-run" not in a
@@ -58,7 +61,8 @@ def test_every_rank_gets_its_pcie_child(gpus):
         assert a[a.index("--gpus") + 1] == "1" and a.count("--gpus") == 1
         assert a[a.index("--xfer-shard") + 1] == "%d/%d" % (r, gpus)
         assert c["env"]["GPU_MAX_HW_QUEUES"] == "8"
-        assert c["env"]["HIP_VISIBLE_DEVICES"] == (str(r) if gpus > 1 else os.environ.get("HIP_VISIBLE_DEVICES"))
+        rank_gpu = ids[r % len(ids)] if ids else str(r)
+        assert c["env"]["HIP_VISIBLE_DEVICES"] == (rank_gpu if gpus > 1 else os.environ.get("HIP_VISIBLE_DEVICES"))
         assert c["rank_env_dropped"] and c["before_gpu_init"]
 
 
