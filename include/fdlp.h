@@ -533,6 +533,55 @@ int fdlp_rnn_compute(fdlp_rnn_plan* plan, const fdlp_post_batch* batch, int32_t 
 int fdlp_rnn_set_profiling(fdlp_rnn_plan* plan, int32_t on);
 int fdlp_rnn_times(fdlp_rnn_plan* plan, double* ms);
 
+/* ---- dump-multimod-outputs: multi-stream GRU models after n_streams chains -------------------- */
+/* nnetRNNMultimod of the reference (src/nnet/nnet_models.py:92-161; dump_multimod_outputs.py): stream s, the rows
+ * of its own chain post[s] (its own cmvn and splice; every stream gives in_dim columns), runs through sub-network s,
+ * n_sub_layers nn.GRU of hidden_sub = Hs units; the M = n_streams outputs side by side, [rows, M Hs], run through
+ * n_trunk_layers nn.GRU of M Hs units and the regression [n_classes, M Hs].  Every GRU is the stage of fdlp_rnn_*
+ * above, bit for bit: layer 0's projection inside its stream's chain launch, later projections in dense_kernel, the
+ * scan in gru_scan_kernel.  The M scans of a sub-network layer are ONE launch on the grid (groups, streams), so a
+ * batch of n utterances keeps M ceil(n / 32) CUs busy there; the last sub-network layer writes stream s at column
+ * s Hs of the concatenated buffer (row stride M Hs), which is never assembled by a copy.  The streams' pointers
+ * travel in the kernel arguments, at most FDLP_MMOD_MAX_STREAMS of them.  An utterance's bits in stream s depend on
+ * Hs and that utterance's rows of stream s alone.  The trunk's width is limited like any GRU's: M Hs <= 384. */
+#define FDLP_MMOD_MAX_STREAMS 8
+typedef struct fdlp_mmod_config {
+  int32_t n_streams;                              /* 1 .. FDLP_MMOD_MAX_STREAMS                                   */
+  fdlp_post_config post[FDLP_MMOD_MAX_STREAMS];   /* per stream; post[0].device is the plan's device              */
+  int32_t in_dim;                                 /* the width every stream's chain must give                      */
+  int32_t n_sub_layers, hidden_sub;               /* >= 1 (at most FDLP_RNN_MAX_STAGES layers)                      */
+  int32_t n_trunk_layers;                         /* 0 .. FDLP_RNN_MAX_STAGES                                      */
+  int32_t n_classes;
+} fdlp_mmod_config;
+typedef struct fdlp_mmod_plan fdlp_mmod_plan;
+/* params: host float32 pointers in nn.GRU's layout, copied to the device (may be NULL for a host-only plan):
+ * {w_ih, w_hh, b_ih, b_hh} of sub-network 0's layers, then sub-network 1's, ..; then of the trunk's layers; then the
+ * regression's {w [n_classes, M Hs], b}: 4 (M n_sub_layers + n_trunk_layers) + 2 pointers.  The plan allocates five
+ * [max_rows, M Hs] float32 buffers (three hold the projections, two the layers' outputs) and the group table of
+ * ceil(max_utts / 32) groups.  FDLP_E_INVALID with the numbers in the message for n_streams outside its range, a
+ * stream whose chain gives another width than in_dim (the message names the stream), Hs or M Hs above the widest GRU
+ * the LDS holds (the message names M Hs and that limit), a dimension < 1, max_rows < 1 or max_utts < 1. */
+int fdlp_mmod_plan_create(const fdlp_mmod_config* cfg, const float* const* params, int64_t max_rows,
+                          int32_t max_utts, fdlp_mmod_plan** out);
+int fdlp_mmod_plan_destroy(fdlp_mmod_plan* plan);
+/* in_dim; n_taps = n_trunk_layers + 2; tap_dims[n_taps]; the bytes of the workspaces above together; group_utts =
+ * 32; the LDS bytes of gru_scan_kernel at the widest GRU.  Works on a host-only plan.  Any pointer may be NULL. */
+int fdlp_mmod_plan_info(const fdlp_mmod_plan* plan, int32_t* in_dim, int32_t* n_taps, int32_t* tap_dims,
+                        int64_t* workspace_bytes, int32_t* group_utts, int32_t* lds_bytes);
+/* As fdlp_rnn_plan_groups: the one group table all streams share.  Host only. */
+int fdlp_mmod_plan_groups(const fdlp_mmod_plan* plan, const int32_t* lengths, int32_t n_utts, int32_t* group_of,
+                          int32_t* slot_of, int32_t* n_groups);
+/* batches[n_streams], each as for fdlp_rnn_compute; all must hold the same n_utt, n_rows, utt_len and row_off
+ * (FDLP_E_INVALID names the first utterance that differs), each its own in_dev and norm table.  The output goes to
+ * batches[0].out_dev.  tap 0: the logits [n_rows, n_classes] (mode as for fdlp_nnet_compute); tap t in
+ * 1 .. n_trunk_layers: trunk GRU n_trunk_layers - t, counted from the end like the other plans' taps; tap
+ * n_trunk_layers + 1: the concatenated sub-network outputs; both [n_rows, M Hs], raw. */
+int fdlp_mmod_compute(fdlp_mmod_plan* plan, const fdlp_post_batch* batches, int32_t tap, int32_t mode,
+                      const void* prior_dev, float prior_weight, void* stream);
+/* As fdlp_rnn_set_profiling / fdlp_rnn_times: ms[0] the projections and the regression, ms[1] the scans. */
+int fdlp_mmod_set_profiling(fdlp_mmod_plan* plan, int32_t on);
+int fdlp_mmod_times(fdlp_mmod_plan* plan, double* ms);
+
 /* ApplyCmvn / ApplyCmvnReverse as two float32 vectors: out[0 .. dim) = scale, out[dim .. 2 dim) = offset, from the
  * [2, dim + 1] double stats compute-cmvn-stats writes (count = stats[dim]; count < 1 is FDLP_E_INVALID).
  * mean = s0/count; norm_vars: var = s1/count - mean^2 floored at 1e-20 (a warning on stderr), scale = 1/sqrt(var),

@@ -119,6 +119,14 @@ class FdlpRnnConfigC(ctypes.Structure):
                 ("dims", c_i32 * (FDLP_RNN_MAX_STAGES + 1))]
 
 
+FDLP_MMOD_MAX_STREAMS = 8
+
+
+class FdlpMmodConfigC(ctypes.Structure):
+    _fields_ = [("n_streams", c_i32), ("post", FdlpPostConfigC * FDLP_MMOD_MAX_STREAMS), ("in_dim", c_i32),
+                ("n_sub_layers", c_i32), ("hidden_sub", c_i32), ("n_trunk_layers", c_i32), ("n_classes", c_i32)]
+
+
 class FdlpPostBatchC(ctypes.Structure):
     _fields_ = [
         ("n_utt", c_i32), ("norm_mul", c_i32), ("in_dev", c_p), ("n_rows", c_i64), ("row_off", P_i64),
@@ -244,6 +252,14 @@ SIGNATURES = {
     "fdlp_rnn_compute": (c_i32, [c_p, ctypes.POINTER(FdlpPostBatchC), c_i32, c_i32, c_p, ctypes.c_float, c_p]),
     "fdlp_rnn_set_profiling": (c_i32, [c_p, c_i32]),
     "fdlp_rnn_times": (c_i32, [c_p, P_dbl]),
+    "fdlp_mmod_plan_create": (c_i32, [ctypes.POINTER(FdlpMmodConfigC), ctypes.POINTER(c_p), c_i64, c_i32,
+                                      ctypes.POINTER(c_p)]),
+    "fdlp_mmod_plan_destroy": (c_i32, [c_p]),
+    "fdlp_mmod_plan_info": (c_i32, [c_p, P_i32, P_i32, P_i32, P_i64, P_i32, P_i32]),
+    "fdlp_mmod_plan_groups": (c_i32, [c_p, P_i32, c_i32, P_i32, P_i32, P_i32]),
+    "fdlp_mmod_compute": (c_i32, [c_p, ctypes.POINTER(FdlpPostBatchC), c_i32, c_i32, c_p, ctypes.c_float, c_p]),
+    "fdlp_mmod_set_profiling": (c_i32, [c_p, c_i32]),
+    "fdlp_mmod_times": (c_i32, [c_p, P_dbl]),
     "fdlp_cmvn_norm": (c_i32, [P_dbl, c_i32, c_i32, c_i32, c_i32, P_i32, c_i32, ctypes.POINTER(ctypes.c_float)]),
     "fdlp_noise_params_f64": (c_i32, [P_dbl, c_i64, P_i16, c_i64, c_dbl, c_dbl, P_i64, P_dbl]),
     "fdlp_mat_reader_open": (c_i32, [ctypes.c_char_p, ctypes.POINTER(c_p)]),

@@ -312,6 +312,20 @@ size_t gru_lds_bytes(int H);     // LDS bytes of a workgroup
 int gru_max_hidden();            // the largest H whose workgroup fits the 160 KB LDS
 hipError_t launch_gru_scan(const float* G, const float* Whh, const float* bhh, float* out, const GruSlot* slots,
                            int n_groups, int64_t rows, int H, hipStream_t s);
+// The same scan for n_streams independent layers of one width H in one launch, grid (n_groups, n_streams): stream i
+// reads G [rows, 3H], Whh, bhh of entry i and writes row r at out + r ldo (ldo >= H; out = base + i H with
+// ldo = n_streams H puts the streams side by side in one [rows, n_streams H] buffer).  The table travels by value in
+// the kernel arguments.  launch_gru_scan is the case n_streams = 1, ldo = H.
+constexpr int kGruMaxStreams = 8;  // FDLP_MMOD_MAX_STREAMS
+struct GruStream {
+  const float *G, *Whh, *bhh;
+  float* out;
+};
+struct GruStreams {
+  GruStream s[kGruMaxStreams];
+};
+hipError_t launch_gru_scan_streams(const GruStreams& st, int n_streams, int ldo, const GruSlot* slots, int n_groups,
+                                   int64_t rows, int H, hipStream_t s);
 hipError_t checks_nnet(unsigned int* v, bool reset);
 
 // One utterance of a reverb batch (fdlp_reverb): samples at pcm[off, off+T), y at [yoff, yoff+T+R-1).

@@ -309,6 +309,13 @@ hipError_t launch_row_epilogue(float* x, int64_t rows, int C, int mode, const fl
 //     bits depend on that utterance alone: not on its group, its slot, the other lengths or the batch.
 //   * an utterance with len <= t (or an empty slot, len = 0) still takes part in the MFMA with whatever its row of
 //     the h buffer holds; it loads G from a clamped row, stores nothing, and no other row reads its row.
+//   * STREAMS: one launch runs n_streams <= kGruMaxStreams independent layers of the same H over the same group
+//     table (the sub-networks of a multi-stream model): the grid is (groups, streams), and workgroup (g, s) reads
+//     G, W_hh, b_hh and the output base of entry s of a table passed BY VALUE in the kernel arguments (no device
+//     memory; blockIdx.y is uniform, so these are scalar loads).  Row r of the output is out_s + r ldo: ldo = H for
+//     a compact [rows, H] buffer, and out_s = base + s H with ldo = n_streams H writes the streams side by side
+//     into one [rows, n_streams H] buffer, the concatenation the next layer reads.  Nothing else depends on the
+//     stream: an utterance's bits in stream s are those of a one-stream launch on stream s's arrays.
 // -----------------------------------------------------------------------------------------------------------
 constexpr int kGruThreads = 256;
 constexpr int kGruWS = kGruKC + 4;              // floats between rows of a staged W_hh chunk
@@ -340,12 +347,17 @@ __device__ __forceinline__ float gru_gate(float gr, float gz, float gn, float ar
 }
 
 template <bool VEC>
-__global__ __launch_bounds__(kGruThreads) void gru_scan_kernel(const float* __restrict__ G,
-                                                               const float* __restrict__ Whh,
-                                                               const float* __restrict__ bhh,
-                                                               float* __restrict__ out,
+__global__ __launch_bounds__(kGruThreads) void gru_scan_kernel(const GruStreams streams, int n_streams, int ldo,
                                                                const GruSlot* __restrict__ slots, int64_t rows,
                                                                int H) {
+  // this workgroup's layer: blockIdx.y is uniform, so the four pointers are scalar loads from the argument table
+  const int sid = blockIdx.y;
+  FDLP_CHECK(n_streams >= 1 && n_streams <= kGruMaxStreams && sid < n_streams && ldo >= H);
+  const GruStream& my = streams.s[min(sid, kGruMaxStreams - 1)];
+  const float* __restrict__ G = my.G;
+  const float* __restrict__ Whh = my.Whh;
+  const float* __restrict__ bhh = my.bhh;
+  float* __restrict__ out = my.out;
   constexpr int NP = 3 * 32 * (kGruKC / 4) / 64;  // 16-byte pieces of a wave's W_hh chunk per lane: 6
   extern __shared__ float4 gru_sh4[];
   const int HS = gru_hs(H), HB = kGruGU * HS;
@@ -463,10 +475,10 @@ __global__ __launch_bounds__(kGruThreads) void gru_scan_kernel(const float* __re
           if (t >= ln[e]) continue;
           const int u = (e & 3) + 8 * (e >> 2) + 4 * hh;
           const int at = u * HS + j;
-          FDLP_CHECK(at >= 0 && at < HB && r0[e] + t < rows);
+          FDLP_CHECK(at >= 0 && at < HB && r0[e] + t < rows && j < ldo && (r0[e] + t) * ldo + j < rows * ldo);
           const float hv = gru_gate(g[0][e], g[1][e], g[2][e], acc[0][e], acc[1][e], acc[2][e], br, bz, bn, hp[at]);
           hn[at] = hv;
-          out[(r0[e] + t) * H + j] = hv;
+          out[(r0[e] + t) * ldo + j] = hv;
         }
       }
     }
@@ -474,24 +486,38 @@ __global__ __launch_bounds__(kGruThreads) void gru_scan_kernel(const float* __re
   }
 }
 
-hipError_t launch_gru_scan(const float* G, const float* Whh, const float* bhh, float* out, const GruSlot* slots,
-                           int n_groups, int64_t rows, int H, hipStream_t s) {
+hipError_t launch_gru_scan_streams(const GruStreams& st, int n_streams, int ldo, const GruSlot* slots, int n_groups,
+                                   int64_t rows, int H, hipStream_t s) {
   if (n_groups <= 0 || rows <= 0) return hipSuccess;
-  if (H < 1 || H > gru_max_hidden()) return hipErrorInvalidValue;
-  const bool vec = H % 4 == 0 && ((uintptr_t)Whh & 15u) == 0;
+  if (H < 1 || H > gru_max_hidden() || n_streams < 1 || n_streams > kGruMaxStreams || ldo < H)
+    return hipErrorInvalidValue;
+  // one template for the launch: 16-byte loads only where every stream's W_hh allows them
+  bool vec = H % 4 == 0;
+  for (int i = 0; i < n_streams; ++i) {
+    if (!st.s[i].G || !st.s[i].Whh || !st.s[i].bhh || !st.s[i].out) return hipErrorInvalidValue;
+    vec = vec && ((uintptr_t)st.s[i].Whh & 15u) == 0;
+  }
   const size_t lds = gru_lds_bytes(H);
 #define FDLP_GRU_LAUNCH(VEC)                                                                                     \
   do {                                                                                                           \
     if (lds > 65536)                                                                                             \
       (void)hipFuncSetAttribute((const void*)gru_scan_kernel<VEC>, hipFuncAttributeMaxDynamicSharedMemorySize,   \
                                 (int)lds);                                                                       \
-    hipLaunchKernelGGL((gru_scan_kernel<VEC>), dim3((unsigned)n_groups), dim3(kGruThreads), lds, s, G, Whh, bhh, \
-                       out, slots, rows, H);                                                                     \
+    hipLaunchKernelGGL((gru_scan_kernel<VEC>), dim3((unsigned)n_groups, (unsigned)n_streams), dim3(kGruThreads), \
+                       lds, s, st, n_streams, ldo, slots, rows, H);                                              \
   } while (0)
   if (vec) FDLP_GRU_LAUNCH(true);
   else FDLP_GRU_LAUNCH(false);
 #undef FDLP_GRU_LAUNCH
   return hipGetLastError();
+}
+
+// one layer: the one-stream case, rows of out H apart
+hipError_t launch_gru_scan(const float* G, const float* Whh, const float* bhh, float* out, const GruSlot* slots,
+                           int n_groups, int64_t rows, int H, hipStream_t s) {
+  GruStreams st{};
+  st.s[0] = {G, Whh, bhh, out};
+  return launch_gru_scan_streams(st, 1, H, slots, n_groups, rows, H, s);
 }
 
 hipError_t checks_nnet(unsigned int* v, bool reset) { return fdlp_checks_local(v, reset); }

@@ -347,6 +347,13 @@ class NnetRunner(SlotRunner):
         self.plan = self._new_plan(cfg, rows)
 
     def _setup(self, dim):
+        self._setup_front(dim)
+        self._make_plan(self.batch_rows)
+        self.out_dim = self.plan.tap_dim(self.layer)
+        self.slots = [self._slot(self.batch_rows) for _ in range(2)]
+
+    def _setup_front(self, dim):
+        """what lies before the model plan, for features of width dim: the transform, the norm and the prior"""
         self.dim = dim
         torch.cuda.set_device(self.device)
         dev = torch.device("cuda", self.device)
@@ -361,9 +368,6 @@ class NnetRunner(SlotRunner):
             raise ValueError("features of dimension %d for a model of feature dimension %d" % (dim, self.ckpt.feature_dim))
         self.norm = torch.from_numpy(self.norm_host).to(dev) if self.norm_host is not None else None
         self.prior = torch.from_numpy(self.prior_host).to(dev) if self.prior_host is not None else None
-        self._make_plan(self.batch_rows)
-        self.out_dim = self.plan.tap_dim(self.layer)
-        self.slots = [self._slot(self.batch_rows) for _ in range(2)]
 
     def _slot(self, rows):
         sl = _Slot(rows, self.dim, self.out_dim, torch.device("cuda", self.device))
@@ -431,13 +435,18 @@ def _load_prior(path):
         raise ValueError("%s: not a pickled prior vector (%s)" % (path, e))
 
 
-def run_model_tool(prog, a, make_runner, did):
-    """What extract-posterior and dump-genclassifier-outputs do with their parsed arguments `a` (scp, save_file):
-    make_runner() loads the files and returns the runner; `did` opens the final LOG line.  Returns the exit status."""
+def _rspecifier(scp):
+    return scp if _split_specifier(scp)[0] else "scp:" + scp
+
+
+def run_model_tool(prog, a, make_runner, did, scps=None):
+    """What the model tools do with their parsed arguments `a` (scp, save_file): make_runner() loads the files and
+    returns the runner; `did` opens the final LOG line.  scps: the tables of a tool that reads several in step
+    (dump-multimod-outputs), whose runner takes the list.  Returns the exit status."""
     writer = None
     try:
         runner = make_runner()
-        rspec = a.scp if _split_specifier(a.scp)[0] else "scp:" + a.scp
+        rspec = _rspecifier(a.scp) if scps is None else [_rspecifier(s) for s in scps]
         if _split_specifier(a.save_file)[0]:
             wspec = a.save_file
         else:

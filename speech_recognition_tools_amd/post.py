@@ -413,7 +413,8 @@ class SlotRunner:
       _added(sl, extra) the utterance _admit returned `extra` for has been appended to slot sl
       _launch(sl)       copy in, compute, copy out, record sl.done
       _grow(cur, rows)  replace slots[cur] by one of `rows` rows for an utterance longer than a slot
-      _host(v)          what is written for the device's rows v of a batch (the identity here)"""
+      _host(v)          what is written for the device's rows v of a batch (the identity here)
+      _reader(rspec)    the (key, matrix) pairs of the table (MatReader here)"""
 
     def _admit(self, utt):
         return None
@@ -423,6 +424,10 @@ class SlotRunner:
 
     def _host(self, v):
         return v
+
+    def _reader(self, rspecifier):
+        """hook: the (key, matrix) pairs the loop consumes"""
+        return MatReader(rspecifier)
 
     def _drain(self, sl):
         if sl.done is None:
@@ -439,7 +444,7 @@ class SlotRunner:
     def run(self, rspecifier: str, writer: "FeatWriter"):
         self.writer = writer
         cur = 0
-        for utt, m in MatReader(rspecifier):
+        for utt, m in self._reader(rspecifier):
             if self.dim is None and m.shape[0] > 0:
                 self._setup(m.shape[1])
             if m.shape[0] == 0 or m.shape[1] != self.dim:

@@ -18,7 +18,7 @@ pseudo log-likelihoods latgen-faster-mapped consumes.
     counted as an error and skipped, as Kaldi does; anything else is raw.
   * --ae_type=vae samples its latent and --ae_type=vaeenc loads a path hard-coded in the reference: neither is
     reproduced, both exit 1 with a message.  --add_softmax uses the max-subtracted form nnet.py documents.
-Out of scope: training, and the CURL, multimod and CNN models.
+Out of scope: training, and the CURL and CNN models (the multi-stream model is multimod.py).
 
 The plan's compute, the runner, the file readers and the command line's body are nnet.py's (StagePlan, NnetRunner,
 open_checkpoint, read_egs_config, run_model_tool); this module adds the stage list, the GRU checkpoints, the

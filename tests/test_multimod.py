@@ -1,0 +1,652 @@
+"""dump-multimod-outputs: the multi-stream GRU model after M chains (speech_recognition_tools_amd/multimod.py, the
+stream-batched gru_scan_kernel of csrc/fdlp_nnet.hip, fdlp_mmod_* of csrc/fdlp_plan.cpp).
+
+What holds the device to account, none of it fitted to what the device gives:
+
+  * the sub-networks against the EXISTING one-stream scan: columns [s Hs, (s + 1) Hs) of the concatenated tap are
+    bit-identical to a single-stream RnnPlan of stream s's GRU layers on stream s's features.  No tolerance: the
+    existing scan (held to its own bounds by tests/test_rnn.py) is the yardstick, and this is also what shows that
+    the stream index, n_streams, the strided output and the compact buffers change no bit;
+  * every trunk stage against ITS OWN device input, with the derived bounds of tests/test_rnn.py
+    (gru_numpy.gru_step_ref_and_bound for a GRU, test_nnet.layer_ref_and_bound for the regression);
+  * against the reference (tests/golden/multimod_*.npz, the float64 forward of the real nnetRNNMultimod):
+    16 x d32 at every tap, the margin test_rnn.test_gpu_against_reference_goldens uses, for its reason;
+  * independence of the batch, of the position and of the other utterances, bitwise;
+  * the footprint: NaN-filled outputs between sentinel guard rows;
+  * softmax and loglike: the bounds of tests/test_rnn.py on the device's own logits.
+"""
+import json
+import os
+import pickle
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import gru_numpy as GN
+import multimod_numpy as MN
+import post_numpy as PN
+import test_nnet as TN_
+import test_rnn as TR
+from conftest import GOLDEN, ROOT
+from test_nnet import ark_like, assert_bits_equal, layer_ref_and_bound, split_rows, stats_of, two_norms
+
+BIN = os.path.join(ROOT, "bin")
+GU, GKC = TR.GU, TR.GKC
+GOLDENS = ["multimod_3", "multimod_deep", "multimod_tiny"]
+NAMES = ["fdlp_mmod_plan_create", "fdlp_mmod_plan_destroy", "fdlp_mmod_plan_info", "fdlp_mmod_plan_groups",
+         "fdlp_mmod_compute", "fdlp_mmod_set_profiling", "fdlp_mmod_times"]
+
+
+def gru_layers(rng, k0, n, H):
+    return [st[1:] for st in TR.make_stages(rng, k0, [("gru", H)] * n)]
+
+
+def make_model(rng, in_dim, M, Ls, Hs, Lt, C):
+    """(subnets [M][Ls], trunk [Lt], regression) with test_rnn.make_stages' weights (torch's init x 3)"""
+    subnets = [gru_layers(rng, in_dim, Ls, Hs) for _ in range(M)]
+    trunk = gru_layers(rng, M * Hs, Lt, M * Hs)
+    return subnets, trunk, TR.make_stages(rng, M * Hs, [("linear", C)])[0][1:]
+
+
+def load_golden(name):
+    z = np.load(os.path.join(GOLDEN, name + ".npz"))
+    meta = json.loads(str(z["meta"]))
+    taps = np.load(os.path.join(GOLDEN, meta["taps_file"])) if meta["taps_file"] else z
+    return meta, z, taps
+
+
+def golden_checkpoint(meta, z):
+    return TR.golden_checkpoint(meta, z)
+
+
+def load_golden_model(name, tmp):
+    import torch
+    from speech_recognition_tools_amd.multimod import load_multimod_checkpoint
+    meta, z, taps = load_golden(name)
+    p = os.path.join(str(tmp), name + ".mdl")
+    torch.save(golden_checkpoint(meta, z), p)
+    return meta, z, taps, load_multimod_checkpoint(p), p
+
+
+def golden_norms(meta, z):
+    return [PN.cmvn_norm(z["stats_%d" % s], norm_vars=True) if meta["feat_type"] == "cmvn" else None
+            for s in range(meta["mod_num"])]
+
+
+# ---------------------------------------------------------------------------------------------
+# CPU
+# ---------------------------------------------------------------------------------------------
+def test_cli_argparse_surface_matches_reference():
+    from speech_recognition_tools_amd import multimod
+    ref = json.load(open(os.path.join(GOLDEN, "cli_options_multimod.json")))
+    assert [o["name"] for o in ref][:4] == ["model", "scps", "egs_configs", "save_file"] and len(ref) == 8
+    a = multimod.dump_multimod_outputs_parser().parse_args(["final.mdl", "a.scp,b.scp", "a.cfg,b.cfg", "post"])
+    for o in ref:
+        dest = o["name"].lstrip("-")
+        assert hasattr(a, dest), o
+        if o["name"].startswith("--"):
+            assert getattr(a, dest) == (False if o.get("action") == "store_true" else o.get("default")), o
+    assert (a.model, a.scps, a.egs_configs, a.save_file) == ("final.mdl", "a.scp,b.scp", "a.cfg,b.cfg", "post")
+    assert (a.ark_precision, a.batch_rows) == (3, 131072)
+    a = multimod.dump_multimod_outputs_parser().parse_args(
+        ["m", "s", "e", "o", "--prior", "p", "--prior_weight", "0.2", "--add_softmax", "--override_trans", "x",
+         "--device", "1", "--batch-rows", "8", "--ark_precision", "-1"])
+    assert (a.prior, a.prior_weight, a.add_softmax, a.override_trans, a.device, a.batch_rows, a.ark_precision) == (
+        "p", 0.2, True, "x", 1, 8, -1)
+    with pytest.raises(SystemExit):
+        multimod.dump_multimod_outputs_parser().parse_args(["m", "s", "e"])
+    assert os.access(os.path.join(BIN, "dump-multimod-outputs"), os.X_OK)
+
+
+@pytest.mark.parametrize("name", GOLDENS)
+def test_checkpoint_round_trip(tmp_path, name):
+    meta, z, _, c, _ = load_golden_model(name, tmp_path)
+    M, Ls, Hs, Lt = meta["mod_num"], meta["num_layers_subband"], meta["hidden_dim_subband"], meta["num_layers"]
+    assert (c.feature_dim, c.num_frames, c.num_classes, c.mod_num) == (
+        meta["feature_dim"], meta["num_frames"], meta["num_classes"], M)
+    assert len(c.subnets) == M and all(len(sn) == Ls for sn in c.subnets) and len(c.trunk) == Lt
+    K0 = meta["feature_dim"] * meta["num_frames"]
+    assert c.subnets[M - 1][0][0].shape == (3 * Hs, K0) and c.subnets[0][Ls - 1][1].shape == (3 * Hs, Hs)
+    assert_bits_equal(c.subnets[M - 1][Ls - 1][1], z["sd_subnets.%d.layers.%d.weight_hh_l0" % (M - 1, Ls - 1)])
+    assert_bits_equal(c.trunk[Lt - 1][0], z["sd_layers.%d.weight_ih_l0" % (Lt - 1)])
+    assert_bits_equal(c.regression[0], z["sd_regression.weight"][:, :, 0])       # the Conv1d weight, squeezed
+    assert c.regression[0].shape == (meta["num_classes"], M * Hs)
+    for a in [x for sn in c.subnets for l in sn for x in l] + [x for l in c.trunk for x in l] + list(c.regression):
+        assert a.dtype == np.float32 and a.flags.c_contiguous
+
+
+def test_checkpoint_errors_name_the_key(tmp_path):
+    import torch
+    from speech_recognition_tools_amd.multimod import load_multimod_checkpoint
+    p = str(tmp_path / "m.pt")
+    meta, z, _ = load_golden("multimod_3")
+    good = golden_checkpoint(meta, z)
+
+    def variant(hdr=None, drop=None, put=None):
+        d = dict(good, model_state_dict=dict(good["model_state_dict"]))
+        d.update(hdr or {})
+        for k in drop or ():
+            (d if k in d else d["model_state_dict"]).pop(k)
+        if put:
+            d["model_state_dict"].update(put)
+        torch.save(d, p)
+
+    variant()
+    assert load_multimod_checkpoint(p).mod_num == 3
+    variant(hdr={"mod_num": 2})                                         # a stream beyond the header's count
+    with pytest.raises(ValueError, match=r"layers\.0\.weight_ih_l0|subnets\.2\."):
+        load_multimod_checkpoint(p)
+    variant(hdr={"mod_num": 4})
+    with pytest.raises(ValueError, match=r"subnets\.3\.layers\.0\.weight_ih_l0"):
+        load_multimod_checkpoint(p)
+    variant(hdr={"mod_num": 9})
+    with pytest.raises(ValueError, match="mod_num"):
+        load_multimod_checkpoint(p)
+    variant(drop=[k for k in good["model_state_dict"] if k.startswith("subnets.2.")])
+    with pytest.raises(ValueError, match=r"subnets\.2\.layers\.0\.weight_ih_l0"):
+        load_multimod_checkpoint(p)
+    variant(put={"subnets.1.layers.1.weight_ih_l0": torch.zeros(60, 20)})   # a layer beyond num_layers_subband
+    with pytest.raises(ValueError, match=r"subnets\.1\.layers\.1\."):
+        load_multimod_checkpoint(p)
+    variant(put={"layers.1.bias_hh_l0": torch.zeros(180)})              # a trunk layer beyond num_layers
+    with pytest.raises(ValueError, match=r"layers\.1\."):
+        load_multimod_checkpoint(p)
+    variant(put={"regression.weight": torch.zeros(10, 40, 1)})          # the regression's width is not M Hs
+    with pytest.raises(ValueError, match=r"regression\.weight"):
+        load_multimod_checkpoint(p)
+    variant(hdr={"hidden_dim_subband": 21})
+    with pytest.raises(ValueError, match=r"subnets\.0\.layers\.0\.weight_ih_l0"):
+        load_multimod_checkpoint(p)
+    for k in ("mod_num", "hidden_dim_subband", "num_layers_subband", "model_state_dict", "regression.bias",
+              "layers.0.weight_hh_l0"):
+        variant(drop=[k])
+        with pytest.raises(ValueError, match=k.replace(".", r"\.")):
+            load_multimod_checkpoint(p)
+    with pytest.raises(OSError, match="absent.pt"):
+        load_multimod_checkpoint(str(tmp_path / "absent.pt"))
+
+
+def _files(d, meta, z):
+    """the fixture as the files the command reads; returns (mdl, scps, egs paths)"""
+    import torch
+    from speech_recognition_tools_amd.cmvn import write_kaldi_dmatrix
+    mdl = d + "/final.mdl"
+    torch.save(golden_checkpoint(meta, z), mdl)
+    scps, egs = [], []
+    for s in range(meta["mod_num"]):
+        ft = None
+        if meta["feat_type"] == "cmvn":
+            write_kaldi_dmatrix("%s/cmvn%d.stats" % (d, s), z["stats_%d" % s])
+            ft = "cmvn,%s/cmvn%d.stats" % (d, s)
+        pickle.dump({"feat_type": ft, "concat_feats": "%d,%d" % (meta["left"], meta["right"])},
+                    open("%s/egs%d.config" % (d, s), "wb"))
+        egs.append("%s/egs%d.config" % (d, s))
+        scps.append(TN_._write_feats(d, "feats%d" % s, [(u, z["in_%d_%s" % (s, u)]) for u in meta["utts"]]))
+    return mdl, scps, egs
+
+
+def test_stream_count_mismatches_exit_1(tmp_path, capsys):
+    from speech_recognition_tools_amd.multimod import main_dump_multimod_outputs
+    meta, z, _ = load_golden("multimod_3")
+    d = str(tmp_path)
+    os.mkdir(d + "/in")
+    mdl, scps, egs = _files(d + "/in", meta, z)
+    os.mkdir(d + "/out")
+    rc = main_dump_multimod_outputs([mdl, ",".join(scps), ",".join(egs[:2]), d + "/out/o"])
+    assert rc == 1 and "Modulation numbers not matching number of egs.config files given!" in capsys.readouterr().err
+    rc = main_dump_multimod_outputs([mdl, ",".join(scps + scps[:1]), ",".join(egs), d + "/out/o"])
+    assert rc == 1 and "Number of modulations does not match with number of scp files given!" in capsys.readouterr().err
+    rc = main_dump_multimod_outputs([d + "/absent.mdl", ",".join(scps), ",".join(egs), d + "/out/o"])
+    assert rc == 1 and "absent.mdl" in capsys.readouterr().err
+    assert os.listdir(d + "/out") == []
+
+
+def test_host_only_plan_info_and_refusals():
+    from speech_recognition_tools_amd._lib import FDLP_E_INVALID, FdlpError
+    from speech_recognition_tools_amd.multimod import MultimodPlan
+    from speech_recognition_tools_amd.post import PostConfig
+    cfg = PostConfig(dim=13, left_context=4, right_context=4)
+    # the recipe's model: 3 streams x 100, trunk 300, 1 + 1 layers, 40 classes
+    p = MultimodPlan([cfg] * 3, None, max_rows=1000, max_utts=70, device=-1, shape=(117, 1, 100, 1, 40))
+    assert (p.in_dim, p.n_streams, p.n_taps, p.tap_dims, p.out_dim) == (117, 3, 3, [40, 300, 300], 40)
+    assert (p.n_sub_layers, p.hidden_sub, p.n_trunk_layers, p.group_utts) == (1, 100, 1, GU)
+    # five [max_rows, M Hs] buffers (three hold the projections), ceil(max_utts / GU) groups of GU 16-byte slots
+    assert p.workspace_bytes == 4 * 1000 * 5 * 300 + 16 * GU * 3
+    # the widest scan is the trunk's: slot table, two [GU, ceil(H / 16) 16 + 4] states, four waves x two W_hh chunks
+    assert p.lds_bytes == 4 * (3 * GU + 2 * GU * (304 + 4) + 4 * 2 * 96 * (GKC + 4))
+    assert [p.tap_dim(t) for t in range(3)] == [40, 300, 300]
+    with pytest.raises(ValueError):
+        p.tap_dim(3)
+    q = MultimodPlan([cfg], None, max_rows=7, max_utts=1, device=-1, shape=(117, 2, 33, 0, 5))
+    assert (q.n_taps, q.tap_dims) == (2, [5, 33])
+    assert q.workspace_bytes == 4 * 7 * 5 * 33 + 16 * GU
+    assert q.lds_bytes == 4 * (3 * GU + 2 * GU * (48 + 4) + 4 * 2 * 96 * (GKC + 4))
+    g, s, ng = p.groups([5, 1, 9, 9, 2] + [3] * GU)
+    assert ng == 2 and (g[2], s[2], g[3], s[3]) == (0, 0, 0, 1) and g[1] == 1
+    # shapes taken from the arrays; streams of different D and context with one spliced width
+    sub, trunk, reg = make_model(np.random.default_rng(0), 27, 2, 2, 6, 1, 4)
+    m = MultimodPlan([PostConfig(dim=9, left_context=1, right_context=1), PostConfig(dim=27)], sub, trunk, reg,
+                     max_rows=5, device=-1)
+    assert (m.in_dim, m.n_sub_layers, m.hidden_sub, m.n_trunk_layers, m.tap_dims) == (27, 2, 6, 1, [4, 12, 12])
+
+    def refused(*need, cfgs=(cfg,) * 3, shape=(117, 1, 100, 1, 40), **kw):
+        a = dict(max_rows=10, max_utts=4, device=-1)
+        a.update(kw)
+        with pytest.raises(FdlpError) as e:
+            MultimodPlan(list(cfgs), None, shape=shape, **a)
+        assert e.value.code == FDLP_E_INVALID and all(n in str(e.value) for n in need), str(e.value)
+
+    refused("387", "384", shape=(117, 1, 129, 1, 40))                   # 3 x 129: the trunk does not fit the LDS
+    MultimodPlan([cfg] * 3, None, max_rows=10, device=-1, shape=(117, 1, 128, 1, 40))   # 3 x 128 = 384 does
+    refused("768", "384", shape=(117, 1, 256, 1, 40))                   # the 3 x 256 of the issue
+    refused("400", "384", cfgs=(cfg,), shape=(117, 1, 400, 0, 40))      # Hs alone beyond it
+    refused("n_streams = 0", cfgs=())
+    refused("n_streams = 9", cfgs=(cfg,) * 9)
+    refused("stream 1", "108", "117", cfgs=(cfg, PostConfig(dim=12, left_context=4, right_context=4), cfg))
+    refused("n_sub_layers", shape=(117, 0, 100, 1, 40))
+    refused("n_classes 0", shape=(117, 1, 100, 1, 0))
+    refused("max_rows", "0", max_rows=0)
+    refused("max_utts", "0", max_utts=0)
+
+
+def test_entry_points_are_declared_and_exported():
+    import ctypes
+    import re
+    from speech_recognition_tools_amd import _lib
+    from speech_recognition_tools_amd.multimod import MultimodPlan
+    from speech_recognition_tools_amd.post import PostConfig
+    src = open(os.path.join(ROOT, "include", "fdlp.h")).read()
+    declared = set(re.findall(r"\b(fdlp_[a-z0-9_]+)\s*\(", src))
+    for n in NAMES:
+        assert n in declared and n in _lib.SIGNATURES and hasattr(_lib.lib, n), n
+    assert sorted(n for n in _lib.SIGNATURES if "mmod" in n) == sorted(NAMES)
+    assert "#define FDLP_MMOD_MAX_STREAMS 8" in src and _lib.FDLP_MMOD_MAX_STREAMS == 8
+    assert ctypes.sizeof(_lib.FdlpMmodConfigC) == 4 * (1 + 7 * 8 + 5)
+    p = MultimodPlan([PostConfig(dim=4)], None, device=-1, shape=(4, 1, 3, 1, 2))
+    with pytest.raises(_lib.FdlpError, match="host-only"):               # a host-only plan refuses to compute
+        _lib.check(_lib.lib.fdlp_mmod_compute(p._h, ctypes.byref(_lib.FdlpPostBatchC()), 0, 0, None, 0.8, None))
+    with pytest.raises(_lib.FdlpError):
+        _lib.check(_lib.lib.fdlp_mmod_plan_info(None, None, None, None, None, None, None))
+
+
+@pytest.mark.parametrize("name", GOLDENS)
+def test_golden_self_check(tmp_path, name):
+    """the restatement and the fixtures agree before any GPU is involved: multimod_numpy in float64 reproduces the
+    real class's float64 taps at every stage (far inside d32)"""
+    meta, z, taps, c, _ = load_golden_model(name, tmp_path)
+    d32, M = meta["d32"], meta["mod_num"]
+    assert 0 < d32 <= 1e-5
+    assert os.path.getsize(os.path.join(GOLDEN, name + ".npz")) <= os.path.getsize(os.path.join(GOLDEN, "rnn_noae.npz"))
+    norms = golden_norms(meta, z)
+    w64 = w32 = 0.0
+    for u in meta["utts"]:
+        rows = [PN.post(z["in_%d_%s" % (s, u)], norms[s], norms[s] is not None, 0, 2, 0, meta["left"], meta["right"])
+                for s in range(M)]
+        s64, t64, l64 = MN.forward(rows, c.subnets, c.trunk, c.regression, np.float64)
+        _, _, l32 = MN.forward(rows, c.subnets, c.trunk, c.regression, np.float32)
+        pairs = ([(s64[s], taps["sub%d_%s" % (s, u)]) for s in range(M)]
+                 + [(t64[l], taps["trunk%d_%s" % (l, u)]) for l in range(meta["num_layers"])] + [(l64, z["f64_" + u])])
+        for a, ref in pairs:
+            assert ref.dtype == np.float64 and ref.shape == a.shape
+            w64 = max(w64, float(np.abs(a - ref).max()))
+        assert l32.dtype == np.float32
+        w32 = max(w32, float(np.abs(l32 - z["f64_" + u]).max()))
+        assert float(np.abs(z["f32_" + u] - z["f64_" + u]).max()) <= d32
+        assert np.all(np.abs(z["logits3_" + u] - z["f32_" + u]) <= 0.0005 + 1e-6)
+    print("%s: float64 restatement within %.3g, float32 within %.3g = %.2f d32" % (name, w64, w32, w32 / d32))
+    assert w64 <= 1e-12 <= d32          # float32 is printed only: multimod_tiny's d32 is a lucky 1e-7 of six rows
+
+
+# ---------------------------------------------------------------------------------------------
+# GPU
+# ---------------------------------------------------------------------------------------------
+def run_mm(plan, xs, norms=None, idx=None, out=None, lengths=None, **kw):
+    """xs[s][u]: stream s's utterance u; norms[s]: None or a list of [2, D] pairs, idx[s] its index list"""
+    import torch
+    feats = [torch.from_numpy(np.concatenate(x)).cuda() for x in xs]
+    nt = [torch.from_numpy(np.stack(n)).cuda() if n is not None else None for n in norms] if norms is not None else None
+    if kw.get("prior") is not None:
+        kw["prior"] = torch.from_numpy(kw["prior"]).cuda()
+    o = plan.compute(feats, lengths if lengths is not None else [x.shape[0] for x in xs[0]], norms=nt,
+                     norm_indexes=idx, out=out, **kw)
+    torch.cuda.synchronize()
+    return o.cpu().numpy()
+
+
+CYCLE = TR.CYCLE
+# name: ([(D, L, R)] per stream, Ls, Hs, Lt, C, lengths)
+CASES = {
+    "a_tails": ([(9, 1, 1)] * 3, 1, 33, 1, 5, [1, 2, 37]),                        # unit and k tails
+    "b_two_groups": ([(5, 1, 1)] * 2, 2, 40, 1, 6, [CYCLE[i % 4] for i in range(GU + 1)]),   # compact, then strided
+    "c_one_unit": ([(4, 0, 0)], 1, 1, 1, 3, [6, 1, 3]),
+    "d_eight_streams": ([(4, 0, 0)] * 8, 1, 5, 1, 3, [3, 1, 7]),
+    "e_trunk384": ([(4, 0, 0)] * 3, 1, 128, 1, 3, [3, 1, 2]),                     # the widest trunk
+    "f_mixed_chains": ([(9, 1, 1), (27, 0, 0)], 1, 12, 1, 4, [4, 1, 9]),
+}
+_built = {}
+
+
+def case(name):
+    """the case's model, plan, inputs and device taps, computed once and shared (nothing modifies them)"""
+    from speech_recognition_tools_amd.multimod import MultimodPlan
+    from speech_recognition_tools_amd.post import PostConfig
+    if name in _built:
+        return _built[name]
+    chains, Ls, Hs, Lt, C, lens = CASES[name]
+    rng = np.random.default_rng(sum(map(ord, name)))
+    M, in_dim = len(chains), chains[0][0] * (chains[0][1] + chains[0][2] + 1)
+    cfgs = [PostConfig(dim=D, left_context=L, right_context=R) for D, L, R in chains]
+    sub, trunk, reg = make_model(rng, in_dim, M, Ls, Hs, Lt, C)
+    xs = [[ark_like(rng, T, D, 2.0 * ((i + s) % 2)) for i, T in enumerate(lens)] for s, (D, _, _) in enumerate(chains)]
+    ni = [two_norms(x) for x in xs]
+    norms, idx = [n for n, _ in ni], [i for _, i in ni]
+    plan = MultimodPlan(cfgs, sub, trunk, reg, max_rows=sum(lens), max_utts=len(lens))
+    taps = [run_mm(plan, xs, norms, idx, tap=t) for t in range(Lt + 2)]
+    _built[name] = dict(cfgs=cfgs, sub=sub, trunk=trunk, reg=reg, xs=xs, norms=norms, idx=idx, plan=plan, taps=taps,
+                        lens=lens, M=M, Hs=Hs, Lt=Lt, C=C)
+    return _built[name]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", sorted(CASES))
+def test_gpu_subnetworks_bit_identical_to_the_one_stream_scan(name):
+    from speech_recognition_tools_amd.rnn import RnnPlan
+    c = case(name)
+    cat = c["taps"][c["Lt"] + 1]
+    rows, M, Hs = sum(c["lens"]), c["M"], c["Hs"]
+    assert cat.shape == (rows, M * Hs) and np.all(np.isfinite(cat))
+    for s in range(M):
+        one = RnnPlan(c["cfgs"][s], [("gru",) + tuple(l) for l in c["sub"][s]], max_rows=rows, max_utts=len(c["lens"]))
+        want = TR.run_rnn(one, c["xs"][s], c["norms"][s], c["idx"][s])
+        assert_bits_equal(cat[:, s * Hs:(s + 1) * Hs], want, "%s stream %d" % (name, s))
+        assert float(np.abs(want).max()) > 0.05                         # not a comparison of zeros
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["a_tails", "b_two_groups", "e_trunk384"])
+def test_gpu_trunk_and_regression_against_their_own_input(name):
+    c = case(name)
+    Lt, xs0 = c["Lt"], c["xs"][0]
+    prev = c["taps"][Lt + 1]
+    for l in range(Lt + 1):
+        got = c["taps"][Lt - l]
+        assert np.all(np.isfinite(got))
+        if l < Lt:
+            pairs = [GN.gru_step_ref_and_bound(a, g, *c["trunk"][l]) for a, g in zip(split_rows(prev, xs0), split_rows(got, xs0))]
+            ref, bound = np.concatenate([p[0] for p in pairs]), np.concatenate([p[1] for p in pairs])
+        else:
+            ref, bound = layer_ref_and_bound(prev, *c["reg"])
+        err = np.abs(got.astype(np.float64) - ref)
+        print("%s trunk stage %d (%s), K %d N %d: max err %.3g, median bound %.3g, max err/bound %.3g"
+              % (name, l, "gru" if l < Lt else "regression", prev.shape[1], got.shape[1], float(err.max()),
+                 float(np.median(bound)), float((err / bound).max())))
+        assert got.shape == ref.shape and np.all(err <= bound), (name, l, float((err - bound).max()))
+        prev = got
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", GOLDENS)
+def test_gpu_against_reference_goldens(tmp_path, name):
+    from speech_recognition_tools_amd.multimod import MultimodPlan
+    from speech_recognition_tools_amd.post import PostConfig
+    meta, z, taps, c, _ = load_golden_model(name, tmp_path)
+    d32, M, Lt, Hs = meta["d32"], meta["mod_num"], meta["num_layers"], meta["hidden_dim_subband"]
+    cfg = PostConfig(dim=meta["feature_dim"], left_context=meta["left"], right_context=meta["right"])
+    xs = [[z["in_%d_%s" % (s, u)] for u in meta["utts"]] for s in range(M)]
+    gn = golden_norms(meta, z)
+    norms = [[n] for n in gn] if gn[0] is not None else None
+    plan = MultimodPlan([cfg] * M, c.subnets, c.trunk, c.regression, max_rows=sum(x.shape[0] for x in xs[0]),
+                        max_utts=len(xs[0]))
+    got = [split_rows(run_mm(plan, xs, norms, None, tap=t), xs[0]) for t in range(Lt + 2)]
+    worst = 0.0
+    for i, u in enumerate(meta["utts"]):
+        pairs = [("sub%d" % s, got[Lt + 1][i][:, s * Hs:(s + 1) * Hs], taps["sub%d_%s" % (s, u)]) for s in range(M)]
+        pairs += [("trunk%d" % l, got[Lt - l][i], taps["trunk%d_%s" % (l, u)]) for l in range(Lt)]
+        pairs.append(("regression", got[0][i], z["f64_" + u]))
+        for what, g, ref in pairs:
+            err = float(np.abs(g.astype(np.float64) - ref).max())
+            print("%s %s %s: max err %.3g = %.3g d32" % (name, u, what, err, err / d32))
+            worst = max(worst, err / d32)
+    assert worst <= 16, worst
+
+
+@pytest.mark.gpu
+def test_gpu_an_utterance_does_not_depend_on_its_batch():
+    from speech_recognition_tools_amd.multimod import MultimodPlan
+    c, rng = case("b_two_groups"), np.random.default_rng(77)
+    others = [[ark_like(rng, 1 + (7 * i) % 11, 5, 1.0 + s) for i in range(GU + 1)] for s in range(2)]
+    norms = [[PN.cmvn_norm(stats_of(np.concatenate(o)), norm_vars=True)] for o in others]
+    rows = sum(o.shape[0] for o in others[0]) + 2 * 12
+    plan = MultimodPlan(c["cfgs"], c["sub"], c["trunk"], c["reg"], max_rows=rows, max_utts=GU + 3)
+    nans = [[np.full_like(o, np.nan) for o in os_] for os_ in others]
+    n = len(others[0])
+    for T in (12, 5, 1):            # the longest, one in the middle of the first group, one of the second group
+        x = [ark_like(rng, T, 5, float(s)) for s in range(2)]
+        for tap in (0, 2):          # the logits and the concatenated tap
+            alone = run_mm(plan, [[x[0]], [x[1]]], norms, tap=tap)
+            assert np.all(np.isfinite(alone)) and alone.shape[0] == T
+
+            def at(batch, k):
+                o = run_mm(plan, batch, norms, tap=tap)
+                off = sum(b.shape[0] for b in batch[0][:k])
+                return o[off:off + T]
+
+            def put(base, k):
+                return [base[s][:k] + [x[s]] + base[s][k:] for s in range(2)]
+
+            assert_bits_equal(at(put(others, 9), 9), alone, "inside a batch")
+            assert_bits_equal(at(put(others, 0), 0), alone, "first in the batch")
+            assert_bits_equal(at(put(others, n), n), alone, "last in the batch")
+            assert_bits_equal(at([b[::-1] for b in put(others, 9)], n - 9), alone, "the batch reversed")
+            twice = [[x[s]] + others[s][:20] + [x[s]] + others[s][20:] for s in range(2)]
+            assert_bits_equal(at(twice, 0), alone, "twice in a batch: the first")
+            assert_bits_equal(at(twice, 21), alone, "twice in a batch: the second")
+            assert_bits_equal(at(put(nans, 9), 9), alone, "among utterances that are NaN in every stream")
+            assert_bits_equal(at(put([others[0], nans[1]], 9), 9), alone, "among utterances that are NaN in stream 1")
+    assert plan.groups([o.shape[0] for o in others[0]] + [1])[0][-1] == 1   # the one-frame target: second group
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["b_two_groups", "d_eight_streams"])
+def test_gpu_footprint_between_guard_rows(name):
+    import torch
+    c = case(name)
+    rows, G, sentinel = sum(c["lens"]), 3, np.float32(-12345.0)
+    for tap in (c["Lt"] + 1, 0):
+        big = torch.full((G + rows + G, c["plan"].tap_dim(tap)), float(sentinel), device="cuda")
+        out = big[G:]
+        out[:rows] = float("nan")
+        got = run_mm(c["plan"], c["xs"], c["norms"], c["idx"], out=out, tap=tap)
+        host = big.cpu().numpy()
+        assert got.shape[0] == rows + G
+        assert np.all(np.isfinite(host[G:G + rows])), "every element of the tapped region is written"
+        assert np.all(host[:G] == sentinel) and np.all(host[G + rows:] == sentinel), "the guard rows are untouched"
+        assert_bits_equal(host[G:G + rows], c["taps"][tap], "the same values as without guards")
+
+
+@pytest.mark.gpu
+def test_gpu_epilogues_and_refusals():
+    from speech_recognition_tools_amd._lib import FDLP_E_INVALID, FdlpError
+    c = case("a_tails")
+    plan, xs, norms, idx, C = c["plan"], c["xs"], c["norms"], c["idx"], c["C"]
+    logits = c["taps"][0]
+    x64 = logits.astype(np.float64)
+    m = x64.max(1, keepdims=True)
+    got = run_mm(plan, xs, norms, idx, mode="softmax")
+    ref = GN.softmax(logits)
+    err = np.abs(got.astype(np.float64) - ref)
+    assert np.all(err <= (C + 8 + (m - x64).max(1, keepdims=True)) * 2.0 ** -23 * ref + 1e-37)
+    prior = np.log(np.random.default_rng(2).dirichlet(np.ones(C))).astype(np.float32)
+    for w in (0.8, 0.2):
+        got = run_mm(plan, xs, norms, idx, mode="loglike", prior=prior, prior_weight=w)
+        w32 = float(np.float32(w))
+        ref = GN.loglike(logits, prior, w32)
+        S = np.exp(x64 - m).sum(1, keepdims=True)
+        bound = (C + 16 + 2 * np.abs(x64 - m) + np.abs(np.log(S)) + np.abs(w32 * prior.astype(np.float64))) * 2.0 ** -23
+        assert np.all(np.abs(got.astype(np.float64) - ref) <= bound)
+    assert_bits_equal(run_mm(plan, xs, norms, idx, mode="raw"), logits)
+    lens = c["lens"]
+    with pytest.raises(FdlpError) as e:                                 # lengths that differ between the streams
+        run_mm(plan, xs, norms, idx, lengths=[lens, lens, [lens[0], lens[1] + 1, lens[2] - 1]])
+    assert e.value.code == FDLP_E_INVALID and "utterance 1" in str(e.value) and "stream 2" in str(e.value), str(e.value)
+    with pytest.raises(ValueError):
+        run_mm(plan, xs, norms, idx, tap=c["Lt"] + 2)                   # a tap out of range
+    with pytest.raises(FdlpError) as e:
+        run_mm(plan, xs, norms, idx, tap=1, mode="softmax")             # a mode on a hidden tap
+    assert e.value.code == FDLP_E_INVALID and "tap" in str(e.value)
+    with pytest.raises(ValueError):
+        run_mm(plan, xs, norms, idx, mode="loglike")                    # no prior
+    with pytest.raises(ValueError):
+        run_mm(plan, xs[:2], norms[:2], idx[:2])                        # a stream short
+    assert_bits_equal(run_mm(plan, xs, norms, idx), logits, "after the refusals")
+
+
+CHECKS_CHILD = r"""
+import json, sys
+sys.path.insert(0, %(root)r)
+sys.path.insert(0, %(tests)r)
+import test_multimod as TM
+from speech_recognition_tools_amd.plan import device_checks
+assert device_checks(reset=True)[0], "not a checks build"
+runs = [len(TM.case(c)["taps"]) for c in TM.CHECK_CASES]
+en, v, line = device_checks()
+print(json.dumps({"enabled": en, "violations": v, "last_line": line, "runs": len(runs)}))
+"""
+CHECK_CASES = ["a_tails", "b_two_groups", "d_eight_streams", "f_mixed_chains"]
+
+
+@pytest.mark.gpu
+def test_gpu_device_range_checks_silent():
+    """the FDLP_DEVICE_CHECKS build: the stream in range, (r0 + t) ldo + j inside the output, and every older check"""
+    lib = os.path.join(ROOT, "speech_recognition_tools_amd", "lib", "libfdlp_checks.so")
+    assert os.path.exists(lib), "build() compiles libfdlp_checks.so"
+    r = subprocess.run([sys.executable, "-c", CHECKS_CHILD % {"root": ROOT, "tests": os.path.join(ROOT, "tests")}],
+                       cwd=ROOT, env=dict(os.environ, FDLP_LIB=lib), capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    res = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert res["enabled"] and res["runs"] == len(CHECK_CASES)
+    assert res["violations"] == 0, res
+
+
+# ---------------------------------------------------------------------------------------------
+# the command, in child processes
+# ---------------------------------------------------------------------------------------------
+def _cli_all(*arglists, timeout=300):
+    """the command once per argument list, the child processes side by side; every one is waited for"""
+    ps = [subprocess.Popen([os.path.join(BIN, "dump-multimod-outputs")] + [str(a) for a in args],
+                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True) for args in arglists]
+    out = []
+    for p in ps:
+        try:
+            so, se = p.communicate(timeout=timeout)
+        except subprocess.TimeoutExpired:
+            p.kill()
+            so, se = p.communicate()
+        out.append(subprocess.CompletedProcess(p.args, p.returncode, so, se))
+    return out
+
+
+@pytest.fixture(scope="module")
+def cli_fix(tmp_path_factory):
+    from speech_recognition_tools_amd.cmvn import write_table
+    from speech_recognition_tools_amd.multimod import load_multimod_checkpoint
+    d = str(tmp_path_factory.mktemp("cli_multimod_3"))
+    meta, z, _ = load_golden("multimod_3")
+    mdl, scps, egs = _files(d, meta, z)
+    utts = meta["utts"]
+    xs = [[z["in_%d_%s" % (s, u)] for u in utts] for s in range(3)]
+    prior = np.log(np.random.default_rng(3).dirichlet(np.ones(meta["num_classes"])))
+    pickle.dump(prior, open(d + "/prior.pkl", "wb"))
+    # stream 1 with per-utterance stats
+    write_table("ark,scp:%s/utt.ark,%s/utt.scp" % (d, d),
+                [(u, stats_of(np.concatenate([x, x[::-1] + 1.0]))) for u, x in zip(utts, xs[1])])
+    pickle.dump({"feat_type": "cmvn_utt," + d + "/utt.scp", "concat_feats": "1,1"}, open(d + "/egs1_utt.config", "wb"))
+    # stream 2 without utt1; stream 1 with utt2 a frame short; stream 1 of another width
+    TN_._write_feats(d, "feats2_missing", [(u, x) for u, x in zip(utts, xs[2]) if u != "utt1"])
+    TN_._write_feats(d, "feats1_short", [(u, x[:-1] if u == "utt2" else x) for u, x in zip(utts, xs[1])])
+    TN_._write_feats(d, "feats1_wide", [(u, np.concatenate([x, x[:, :1]], axis=1)) for u, x in zip(utts, xs[1])])
+    return dict(d=d, meta=meta, z=z, c=load_multimod_checkpoint(mdl), mdl=mdl, scps=scps, egs=egs, utts=utts, xs=xs,
+                prior=prior.astype(np.float32))
+
+
+def _expected(c, norms=None, idx=None, keep=None, **kw):
+    from speech_recognition_tools_amd.multimod import MultimodPlan
+    from speech_recognition_tools_amd.post import PostConfig
+    meta = c["meta"]
+    xs = [[x for i, x in enumerate(st) if keep is None or i in keep] for st in c["xs"]]
+    plan = MultimodPlan([PostConfig(dim=9, left_context=1, right_context=1)] * 3, c["c"].subnets, c["c"].trunk,
+                        c["c"].regression, max_rows=sum(x.shape[0] for x in xs[0]), max_utts=len(xs[0]))
+    if norms is None:
+        norms = [[n] for n in golden_norms(meta, c["z"])]
+    return split_rows(run_mm(plan, xs, norms, idx, **kw), xs[0])
+
+
+@pytest.mark.gpu
+def test_gpu_cli_logits_and_batches(cli_fix):
+    from speech_recognition_tools_amd.nnet import round_ark
+    c, d = cli_fix, cli_fix["d"]
+    scps, egs = ",".join(c["scps"]), ",".join(c["egs"])
+    r, r1, r24 = _cli_all([c["mdl"], scps, egs, d + "/post", "--override_trans", "ignored"],
+                          [c["mdl"], scps, egs, d + "/post_1", "--batch-rows", "1"],
+                          [c["mdl"], scps, egs, d + "/post_24", "--batch-rows", "24"])
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert r.stderr.count("--override_trans is ignored") == 1
+    assert r.stderr.strip().splitlines()[-1] == ("LOG (dump-multimod-outputs) Dumped outputs for %d utterances, "
+                                                 "errors on 0" % len(c["utts"]))
+    got = TN_._read_scp(d + "/post.scp")
+    assert [k for k, _ in got] == c["utts"]
+    assert not [f for f in os.listdir(d) if f.endswith(".tmp")]
+    for (k, g), w in zip(got, _expected(c)):
+        assert_bits_equal(g, round_ark(w, 3), k)                        # the stated rounding, bit for bit
+        assert np.all(np.abs(g.astype(np.float64) - c["z"]["logits3_" + k]) <= 0.001 + 16 * c["meta"]["d32"]), k
+    for rb, name in ((r1, "post_1"), (r24, "post_24")):                 # byte-identical files
+        assert rb.returncode == 0, rb.stderr[-2000:]
+        assert open("%s/%s.ark" % (d, name), "rb").read() == open(d + "/post.ark", "rb").read()
+        assert open("%s/%s.scp" % (d, name)).read().replace(name + ".ark", "post.ark") == open(d + "/post.scp").read()
+
+
+@pytest.mark.gpu
+def test_gpu_cli_prior_softmax_utterance_cmvn_and_skips(cli_fix, tmp_path):
+    from speech_recognition_tools_amd.nnet import round_ark
+    c, d, t = cli_fix, cli_fix["d"], str(tmp_path)
+    scps, egs = ",".join(c["scps"]), ",".join(c["egs"])
+    bad_scps = ",".join([c["scps"][0], d + "/feats1_short.scp", d + "/feats2_missing.scp"])
+    wide_scps = ",".join([c["scps"][0], d + "/feats1_wide.scp", c["scps"][2]])
+    rl, rs, ru, rk, rw, rn = _cli_all(
+        [c["mdl"], scps, egs, d + "/ll", "--prior", d + "/prior.pkl", "--prior_weight", "0.2"],
+        [c["mdl"], scps, egs, d + "/sm", "--add_softmax"],
+        [c["mdl"], scps, ",".join([c["egs"][0], d + "/egs1_utt.config", c["egs"][2]]), d + "/pu"],
+        [c["mdl"], bad_scps, egs, d + "/skip"],
+        [c["mdl"], wide_scps, egs, t + "/o1"],
+        [c["mdl"], scps, ",".join(c["egs"][:2]), t + "/o2"])
+    assert rl.returncode == 0, rl.stderr[-2000:]
+    for (k, g), w in zip(TN_._read_scp(d + "/ll.scp"), _expected(c, mode="loglike", prior=c["prior"], prior_weight=0.2)):
+        assert_bits_equal(g, round_ark(w, 3), k)
+    assert rs.returncode == 0, rs.stderr[-2000:]
+    for (k, g), w in zip(TN_._read_scp(d + "/sm.scp"), _expected(c, mode="softmax")):
+        assert_bits_equal(g, round_ark(w, 3), k)
+        assert np.all(np.abs(g.sum(1) - 1.0) <= c["meta"]["num_classes"] * 0.0005 + 1e-6)
+    # stream 1 normalised per utterance
+    assert ru.returncode == 0, ru.stderr[-2000:]
+    gn = golden_norms(c["meta"], c["z"])
+    norms = [[gn[0]], [PN.cmvn_norm(stats_of(np.concatenate([x, x[::-1] + 1.0])), norm_vars=True) for x in c["xs"][1]],
+             [gn[2]]]
+    got = TN_._read_scp(d + "/pu.scp")
+    assert [k for k, _ in got] == c["utts"]
+    for (k, g), w in zip(got, _expected(c, norms, [None, list(range(len(c["utts"]))), None])):
+        assert_bits_equal(g, round_ark(w, 3), k)
+    # utt1 is missing from stream 2 and utt2 is a frame short in stream 1: skipped, counted, the others as ever
+    assert rk.returncode == 0, rk.stderr[-2000:]
+    assert "utterance utt1 is missing from stream 2" in rk.stderr and "utterance utt2 has" in rk.stderr
+    assert rk.stderr.strip().splitlines()[-1].endswith("for 2 utterances, errors on 2")
+    got = TN_._read_scp(d + "/skip.scp")
+    assert [k for k, _ in got] == ["utt0", "utt3"]
+    for (k, g), w in zip(got, _expected(c, keep=(0, 3))):
+        assert_bits_equal(g, round_ark(w, 3), k)
+    # failures leave nothing behind: features of another width in stream 1 (found after the writer is open), and
+    # an egs.config short
+    assert rw.returncode == 1 and "dimension 10" in rw.stderr, rw.stderr[-2000:]
+    assert rn.returncode == 1 and "Modulation numbers not matching" in rn.stderr, rn.stderr[-2000:]
+    assert os.listdir(t) == []
