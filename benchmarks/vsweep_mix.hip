@@ -5,6 +5,7 @@
 //   lds   : dpp + the window's A new values and cur read from an LDS ring each block (two banks)
 //   ldsdpp / ldsrev / ldsrev0 / ldsrevc : the kernel's own block (v_fmac_f64_dpp broadcasts,
 //           window reads at the block head) in two FMA orders, see krev below
+//   fc22 (argument "fc"): the ldsrev block in the 2x2 fast-correlation form, 75 FMAs per block, see k22 below
 //   kx modes (argument "ctl"): ldsrev plus the kernel's per-block control flow, see kx below
 // The ring rows are 544 doubles, the kernel's conflict-free stride.
 // Build: hipcc -O3 --offload-arch=gfx950 benchmarks/vsweep_mix.hip -o benchmarks/vsweep_mix
@@ -210,6 +211,92 @@ __global__ __launch_bounds__(64, 2) void krev(const double* in, double* out, int
   out[blockIdx.x * 64 + threadIdx.x] = s;
 }
 
+// k22 (mode fc22): the ldsrev block in the 2x2 fast-correlation form.  For even v, u, with g0 = s[n0+v],
+// g1 = s[n0+v+1] and W the lane's window,
+//   Q[u]   += g0        * (W[v+u]   - W[v+u+1])
+//   M[u/2] += (g0 + g1) *  W[v+u+1]
+//   Q[u+1] += g1        * (W[v+u+2] - W[v+u+1])
+// and acc[u] = Q[u] + M[u/2], acc[u+1] = Q[u+1] + M[u/2]: three products per 2 positions x 2 lags, 75 per
+// block instead of 100, plus A subtractions and one addition.  Per bank the wave keeps the signed
+// differences e[q] (even q: W[q] - W[q+1], odd q: W[q+1] - W[q]; e[A-1] crosses into the older bank), the raw
+// odd elements and the raw W[0] (for the next block's e[A-1]); A is even, so the older bank's differences are
+// reused as they are.  curs (lane v = s[n0+v] + s[n0+v+1]) is the second DPP source: one more ring read per
+// block, issued a block ahead like cur's, and the addition.  Same ring row, same window reads, same FMA
+// discipline as ldsrev (ordered v_fmac_f64_dpp, the 30 products of the older bank first, then the new bank by
+// window element, consecutive FMAs on distinct accumulators).  M is folded into Q after the loop.
+struct Bank22 { double e[A], od[A / 2], w0; };
+constexpr int kN22 = 3 * (A / 2) * (A / 2);
+struct Order22 { int src[kN22], v[kN22], acc[kN22], op[kN22], nold; };  // src 0: cur x e[op] -> Q[acc]; 1: curs x W[op] -> M[acc]
+constexpr Order22 make_order22() {
+  Order22 o{};
+  int n = 0;
+  for (int pass = 0; pass < 2; ++pass) {
+    for (int t = pass == 0 ? A : 0; t <= (pass == 0 ? 2 * A - 4 : A - 2); t += 2) {  // tiles with v + u = t
+      const int umax = t < A - 2 ? t : A - 2, umin = t - (A - 2) > 0 ? t - (A - 2) : 0;
+      for (int u = umax; u >= umin; u -= 2) { o.src[n] = 0; o.v[n] = t - u; o.acc[n] = u; o.op[n] = t; ++n; }
+      for (int u = umax; u >= umin; u -= 2) { o.src[n] = 1; o.v[n] = t - u; o.acc[n] = u / 2; o.op[n] = t + 1; ++n; }
+      for (int u = umax; u >= umin; u -= 2) { o.src[n] = 0; o.v[n] = t - u + 1; o.acc[n] = u + 1; o.op[n] = t + 1; ++n; }
+    }
+    if (pass == 0) o.nold = n;
+  }
+  return o;
+}
+template <int I, int END>
+__device__ __forceinline__ void fma22(double (&Q)[A], double (&M)[A / 2], double cm, double csm, const Bank22& lo,
+                                      const Bank22& hi) {
+  if constexpr (I < END) {
+    constexpr Order22 o = make_order22();
+    constexpr int v = o.v[I], a = o.acc[I], op = o.op[I];
+    if constexpr (o.src[I] == 0) fmac_bcast<v, true>(Q[a], cm, op < A ? lo.e[op] : hi.e[op - A]);
+    else fmac_bcast<v, true>(M[a], csm, op < A ? lo.od[op / 2] : hi.od[(op - A) / 2]);
+    fma22<I + 1, END>(Q, M, cm, csm, lo, hi);
+  }
+}
+__global__ __launch_bounds__(64, 2) void k22(const double* in, double* out, int iters) {
+  __shared__ double ring[4][544];
+  const int l = threadIdx.x & 15, row = threadIdx.x >> 4;
+  for (int q = l; q < 544; q += 16) ring[row][q] = in[(q + row) & 255] + 1e-3 * q;
+  __syncthreads();
+  double Q[A], M[A / 2];
+  Bank22 X, Y;
+  for (int u = 0; u < A; ++u) { Q[u] = 0; M[u / 2] = 0; X.e[u] = in[u + l]; Y.e[u] = in[u + 20 + l]; }
+  for (int u = 0; u < A / 2; ++u) { X.od[u] = in[u + 40 + l]; Y.od[u] = in[u + 50 + l]; }
+  X.w0 = in[60 + l]; Y.w0 = in[61 + l];
+  double cur = ring[row][l], cur1 = ring[row][(1 + l) & 511];
+  constexpr int kOld = make_order22().nold;
+  static_assert(kOld == 3 * (A / 2) * (A / 2 - 1) / 2, "older-bank products");
+  auto blk = [&](int n0, Bank22& lo, const Bank22& hi) {
+    const int base = (n0 + A * l) & 510;
+    double r[A];
+#pragma unroll
+    for (int q = 0; q < A; ++q) r[q] = ring[row][base + q];
+    const double c = cur, cs = cur + cur1;
+    cur = ring[row][(n0 + A + l) & 511];
+    cur1 = ring[row][(n0 + A + 1 + l) & 511];
+    double cm, csm;
+    asm volatile("v_mov_b64 %0, %2\n\tv_mov_b64 %1, %3\n\ts_nop 1" : "=&v"(cm), "=&v"(csm) : "v"(c), "v"(cs));
+    fma22<0, kOld>(Q, M, cm, csm, lo, hi);
+    // the window is taken in behind the older bank's products
+#pragma unroll
+    for (int q = 0; q < A; ++q) asm volatile("" : "+v"(r[q]));
+#pragma unroll
+    for (int q = 0; q + 1 < A; ++q) lo.e[q] = (q & 1) ? r[q + 1] - r[q] : r[q] - r[q + 1];
+    lo.e[A - 1] = hi.w0 - r[A - 1];
+#pragma unroll
+    for (int q = 0; q < A / 2; ++q) lo.od[q] = r[2 * q + 1];
+    lo.w0 = r[0];
+    fma22<kOld, kN22>(Q, M, cm, csm, lo, hi);
+  };
+  for (int it = 0; it < iters; ++it) {
+    const int n0 = (it * 2 * A) & 511;
+    blk(n0, X, Y);
+    blk(n0 + A, Y, X);
+  }
+  double s = 0;
+  for (int u = 0; u < A; ++u) s += Q[u] + M[u / 2];
+  out[blockIdx.x * 64 + threadIdx.x] = s;
+}
+
 // kx: ldsrev (krev<1, true, true>) plus the per-block control flow that ac_vsweep_kernel's block carries and
 // the microbenchmark's does not, one piece at a time.  Every test is wave-uniform and never true at run time
 // (its operands are kernel arguments and table words, so the compiler keeps it); what is priced is the
@@ -327,12 +414,13 @@ static void launch(dim3 g, const double* in, double* out, int iters) {
   else if constexpr (MODE == 6) hipLaunchKernelGGL((krev<1, true, true>), g, dim3(64), 0, 0, in, out, iters);
   else if constexpr (MODE == 7) hipLaunchKernelGGL((krev<1, false, true>), g, dim3(64), 0, 0, in, out, iters);
   else if constexpr (MODE == 8) hipLaunchKernelGGL((krev<1, true, false>), g, dim3(64), 0, 0, in, out, iters);
+  else if constexpr (MODE == 9) hipLaunchKernelGGL(k22, g, dim3(64), 0, 0, in, out, iters);
   else if constexpr (MODE == 4) hipLaunchKernelGGL(kdw, g, dim3(64), 0, 0, in, out, iters);
   else if constexpr (MODE == 3) hipLaunchKernelGGL(kpf, g, dim3(64), 0, 0, in, out, iters);
   else hipLaunchKernelGGL(k<MODE>, g, dim3(64), 0, 0, in, out, iters);
 }
 template <int MODE>
-static void run(const char* name, const double* in, double* out, int waves, int iters) {
+static void run(const char* name, const double* in, double* out, int waves, int iters, bool blocks_too = false) {
   hipEvent_t a, b;
   hipEventCreate(&a); hipEventCreate(&b);
   launch<MODE>(dim3(waves), in, out, 10);
@@ -343,12 +431,17 @@ static void run(const char* name, const double* in, double* out, int waves, int 
   float ms = 0;
   hipEventElapsedTime(&ms, a, b);
   const double flops = (MODE == 3 ? 1.0 : 2.0) * 2 * A * A * 64.0 * waves * (double)iters;  // kpf: one block per it
-  printf("%-8s waves %5d  %.3f ms  %.1f TFLOP/s\n", name, waves, ms, flops / ms / 1e9);
+  if (MODE == 9 || blocks_too)  // fc mode: blocks of A positions per second (all waves), and 200 FLOP per block and lane
+    printf("%-8s waves %5d  %.3f ms  %.3e blocks/s  %.1f effective TFLOP/s\n", name, waves, ms,
+           2.0 * waves * (double)iters / ms * 1e3, flops / ms / 1e9);
+  else
+    printf("%-8s waves %5d  %.3f ms  %.1f TFLOP/s\n", name, waves, ms, flops / ms / 1e9);
 }
 
 // vsweep_mix       : the instruction mixes
 // vsweep_mix ctl   : ldsrev against the kx modes (the kernel's per-block control flow), twice over so that
 //                    the run-to-run spread stands next to the differences
+// vsweep_mix fc    : ldsrev against fc22 (the 2x2 fast-correlation block), alternating, six times over
 int main(int argc, char** argv) {
   double *in, *out;
   hipMalloc(&in, 4096 * sizeof(double));
@@ -356,6 +449,13 @@ int main(int argc, char** argv) {
   double h[4096];
   for (int i = 0; i < 4096; ++i) h[i] = 1.0 + 1e-6 * i;
   hipMemcpy(in, h, sizeof(h), hipMemcpyHostToDevice);
+  if (argc > 1 && !strcmp(argv[1], "fc")) {
+    for (int rep = 0; rep < 6; ++rep) {
+      run<6>("ldsrev", in, out, 2048, 20000, true);
+      run<9>("fc22", in, out, 2048, 20000);
+    }
+    return 0;
+  }
   if (argc > 1 && !strcmp(argv[1], "ctl")) {
     Rec4* tab;
     hipMalloc(&tab, 64 * sizeof(Rec4));

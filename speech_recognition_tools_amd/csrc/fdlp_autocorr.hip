@@ -747,6 +747,65 @@ __device__ __forceinline__ void vs_fma_block(double (&acc)[A], double cur, const
   vs_fma_rows<A>(acc, cm, lo, hi);
 }
 
+// Plain runs in the 2x2 fast-correlation form (vs_fast22): for even v, u, with g0 = s[n0+v], g1 = s[n0+v+1],
+//   Q[u]   += g0        * (W[v+u]   - W[v+u+1])
+//   M[u/2] += (g0 + g1) *  W[v+u+1]
+//   Q[u+1] += g1        * (W[v+u+2] - W[v+u+1])
+// and acc[u] = Q[u] + M[u/2], acc[u+1] = Q[u+1] + M[u/2]: the four direct products of positions v, v+1 at lags
+// u, u+1 from three, so a block issues 3 A^2 / 4 FMAs, A subtractions and one addition.  Q is acc itself; M
+// lives only inside a run and is folded into acc at its end.  Per bank the wave keeps the signed differences
+// e[q] (even q: W[q] - W[q+1], odd q: W[q+1] - W[q]; e[A-1] crosses into the older bank, whose W[0] is kept
+// for it) and the raw odd elements.  A is even and block bases are multiples of A, so the parity of a window
+// index is that of the position and the older bank's differences are reused as they are.  The second DPP
+// source, curs (lane v = s[n0+v] + s[n0+v+1]), costs one more ring read per block, issued a block ahead like
+// cur's.  The order keeps vs_order's rule: the tiles with v + u >= A, which need only the older bank, first,
+// then the new bank by window element; consecutive FMAs write distinct accumulators.
+template <int A>
+struct VsBank22 {
+  double e[A], od[A / 2], w0;
+};
+template <int A>
+struct VsOrder22 {
+  static constexpr int kN = 3 * (A / 2) * (A / 2);
+  int src[kN], v[kN], acc[kN], op[kN], nold;  // src 0: cur x e[op] -> acc[acc]; src 1: curs x W[op] -> M[acc]
+};
+template <int A>
+constexpr VsOrder22<A> vs_order22() {
+  VsOrder22<A> o{};
+  int n = 0;
+  for (int pass = 0; pass < 2; ++pass) {
+    for (int t = pass == 0 ? A : 0; t <= (pass == 0 ? 2 * A - 4 : A - 2); t += 2) {  // the tiles with v + u = t
+      const int umax = t < A - 2 ? t : A - 2, umin = t - (A - 2) > 0 ? t - (A - 2) : 0;
+      for (int u = umax; u >= umin; u -= 2) o.src[n] = 0, o.v[n] = t - u, o.acc[n] = u, o.op[n] = t, ++n;
+      for (int u = umax; u >= umin; u -= 2) o.src[n] = 1, o.v[n] = t - u, o.acc[n] = u / 2, o.op[n] = t + 1, ++n;
+      for (int u = umax; u >= umin; u -= 2) o.src[n] = 0, o.v[n] = t - u + 1, o.acc[n] = u + 1, o.op[n] = t + 1, ++n;
+    }
+    if (pass == 0) o.nold = n;
+  }
+  return o;
+}
+template <int A, int I, int END>
+__device__ __forceinline__ void vs_fma22(double (&acc)[A], double (&M)[A / 2], double cm, double csm,
+                                         const VsBank22<A>& lo, const VsBank22<A>& hi) {
+  if constexpr (I < END) {
+    constexpr VsOrder22<A> o = vs_order22<A>();
+    constexpr int V = o.v[I], U = o.acc[I], W = o.op[I];
+    static_assert(V >= 0 && V < A && W >= 0 && W < 2 * A - 2, "block order");
+    if constexpr (o.src[I] == 0) {
+      static_assert(U < A, "block order");
+      fmac_bcast_ordered<V>(acc[U], cm, W < A ? lo.e[W] : hi.e[W - A]);
+    } else {
+      static_assert(U < A / 2 && (W & 1) == 1 && (V & 1) == 0, "block order");
+      fmac_bcast_ordered<V>(M[U], csm, W < A ? lo.od[W / 2] : hi.od[(W - A) / 2]);
+    }
+    vs_fma22<A, I + 1, END>(acc, M, cm, csm, lo, hi);
+  }
+}
+// Which instantiations run their plain runs in the 2x2 form: those that keep two waves per SIMD without
+// scratch and without a spill in the run loop (the register table).
+template <int A, int C>
+constexpr bool vs_fast22() { return !(A == 8 && C == 4) && !(A == 10 && C >= 6); }
+
 template <int A, int C>
 __global__ __launch_bounds__(64, vs_waves_per_simd<C>()) void ac_vsweep_kernel(DevConsts c, const double* __restrict__ dct,
                                                           double* __restrict__ rlow, double* __restrict__ rup,
@@ -1086,11 +1145,77 @@ __global__ __launch_bounds__(64, vs_waves_per_simd<C>()) void ac_vsweep_kernel(D
     // worked out here in scalar registers from state the wave holds anyway (vs_run_pairs: three divisions by A,
     // ahead of every general pair, also where it comes to 0); fdlp_plan_sweep_schedule replays the walk on
     // the host with the same functions.
+    if constexpr (vs_fast22<A, C>()) {
+      int m = vs_run_pairs(b, b_whole, evS, lo_loaded, b_bot, A);
+      if (m > 0) {
+        // curs' second term, position n0 + 1 + l, from the slot behind cur's: behind the ring's last slot the
+        // mirror holds slot 0 again, so the pair needs one address (and is one ds_read2_b64)
+        double cur1_ahead = rg[slot_add(A * b, l) + 1];
+        // entry: the general block left Y raw; its differences (e[A-1] is never the older bank's) and odd elements
+        VsBank22<A> bx, by;
+#pragma unroll
+        for (int q = 0; q + 1 < A; ++q) by.e[q] = (q & 1) ? Y[q + 1] - Y[q] : Y[q] - Y[q + 1];
+        by.e[A - 1] = 0.0;
+#pragma unroll
+        for (int q = 0; q < A / 2; ++q) by.od[q] = Y[2 * q + 1];
+        by.w0 = Y[0];
+        double M[A / 2];
+#pragma unroll
+        for (int q = 0; q < A / 2; ++q) M[q] = 0.0;
+        auto plain22 = [&](int n0, VsBank22<A>& lo, const VsBank22<A>& hi) __attribute__((always_inline)) {
+          FDLP_CHECK(evS < n0 && n0 >= nlo && n0 + A <= nhi && n0 - A >= A * b_bot);
+          FDLP_CHECK(n0 - A >= lo_loaded && n0 + 16 * A <= lo_loaded + kVsRing);
+          // curs' read for the block below: positions n0 - A + 1 + l, inside the staged range of the line above,
+          // at a slot inside the ring or the first of its mirror
+          FDLP_CHECK(n0 - A + 1 >= lo_loaded && n0 - A + 1 + 15 < lo_loaded + kVsRing);
+          FDLP_CHECK(slot_add(n0 - A, l) + 1 < kVsRing + kVsMirror);
+          const int base = slot_add(n0, A * l);
+          double w[A];
+#pragma unroll
+          for (int q = 0; q < A; ++q) w[q] = rg[base + q];
+          const double cur = cur_ahead, curs = cur_ahead + cur1_ahead;
+          const int ahead = slot_add(n0 - A, l);
+          cur_ahead = rg[ahead];
+          cur1_ahead = rg[ahead + 1];
+          // both DPP sources two wait states past their VALU writes (vs_fma_block)
+          double cm, csm;
+          asm volatile("v_mov_b64 %0, %2\n\tv_mov_b64 %1, %3\n\ts_nop 1" : "=&v"(cm), "=&v"(csm) : "v"(cur), "v"(curs));
+          constexpr int kOld = vs_order22<A>().nold;
+          vs_fma22<A, 0, kOld>(acc, M, cm, csm, lo, hi);
+          // the window is taken in behind the older bank's products
+#pragma unroll
+          for (int q = 0; q < A; ++q) asm volatile("" : "+v"(w[q]));
+#pragma unroll
+          for (int q = 0; q + 1 < A; ++q) lo.e[q] = (q & 1) ? w[q + 1] - w[q] : w[q] - w[q + 1];
+          lo.e[A - 1] = hi.w0 - w[A - 1];
+#pragma unroll
+          for (int q = 0; q < A / 2; ++q) lo.od[q] = w[2 * q + 1];
+          lo.w0 = w[0];
+          vs_fma22<A, kOld, VsOrder22<A>::kN>(acc, M, cm, csm, lo, hi);
+        };
 #pragma unroll 1
-    for (int m = vs_run_pairs(b, b_whole, evS, lo_loaded, b_bot, A); m > 0; --m) {  // (X, Y) pairs: the bank parity is kept
-      plain(A * b, X, Y);
-      plain(A * b - A, Y, X);
-      b -= 2;
+        for (; m > 0; --m) {  // (X, Y) pairs: the bank parity is kept
+          plain22(A * b, bx, by);
+          plain22(A * b - A, by, bx);
+          b -= 2;
+        }
+#pragma unroll
+        for (int u = 0; u < A; ++u) acc[u] += M[u >> 1];
+        // exit: the general block needs the run's last bank raw; it is still staged (vs_plain_low)
+        const int n0 = A * b + A;
+        FDLP_CHECK(n0 >= lo_loaded && n0 + 16 * A <= lo_loaded + kVsRing);
+        const int base = slot_add(n0, A * l);
+        FDLP_CHECK(base >= 0 && base + A <= kVsRing + kVsMirror);
+#pragma unroll
+        for (int q = 0; q < A; ++q) Y[q] = rg[base + q];
+      }
+    } else {
+#pragma unroll 1
+      for (int m = vs_run_pairs(b, b_whole, evS, lo_loaded, b_bot, A); m > 0; --m) {  // (X, Y) pairs: the bank parity is kept
+        plain(A * b, X, Y);
+        plain(A * b - A, Y, X);
+        b -= 2;
+      }
     }
     block(A * b, X, Y);
     if (--b < b_bot) break;
