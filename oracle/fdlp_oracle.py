@@ -232,6 +232,35 @@ def dct_frames(fr: np.ndarray, g: Geometry) -> np.ndarray:
     return _sfft.dct(fr, type=2, axis=-1) / np.sqrt(2 * g.N)
 
 
+def frames_f64(signal: np.ndarray, cfg: FdlpConfig, g: Geometry, diff: bool = False,
+               noise: Optional[np.ndarray] = None, noise_off: int = 0, alpha: float = 0.0) -> np.ndarray:
+    """Windowed float64 frames of one utterance for every input the device accepts: an int16 signal or the
+    float64 values of another WAV dtype, optionally the diff filter (computeFDLPSpectrogram.py:162-164) or
+    noise mixing sig + alp * noise[off:off+T] (features.py:31, any dtype + float64 -> float64), then reflect
+    padding (features.py:146) and frame * np.hamming(N) in float64 (features.py:153)."""
+    if diff and noise is not None:
+        raise ValueError("diff and noise mixing are exclusive (computeFDLPSpectrogram.py:160-166)")
+    x = np.asarray(signal)
+    T = x.shape[0]
+    if diff:
+        x = diff_signal(x)
+    elif noise is not None:
+        x = x + alpha * noise[noise_off:noise_off + T]               # features.py:31
+    x = x.astype(np.float64)                                         # int16 / int64 values are exact
+    F = n_frames(T, g)
+    idx = (np.arange(F)[:, None] * g.hop + np.arange(g.N)[None, :]) - g.ext
+    return x[reflect_index(idx, T)] * np.hamming(g.N)
+
+
+def dct_frames_ld(fr: np.ndarray, g: Geometry) -> np.ndarray:
+    """dct_frames in long double: the yardstick the float64 routes (scipy's and the device's) are held to.
+    Fails on a platform whose long double is no wider than float64 instead of comparing like with like."""
+    x = np.asarray(fr).astype(np.longdouble)
+    D = _sfft.dct(x, type=2, axis=-1) / np.sqrt(np.longdouble(2 * g.N))
+    assert np.finfo(D.dtype).eps < 1e-18, "long double is not extended precision here (%s)" % D.dtype
+    return D
+
+
 def autocorr_fft(band: np.ndarray, nlags: int) -> np.ndarray:
     """Circular autocorrelation, real part, via FFT (features.py:223-225); lags [0, nlags)."""
     F = np.fft.fft(band, band.shape[-1], axis=-1)
