@@ -1,4 +1,4 @@
-// fdlp_internal.h -- structures shared by the host runtime (fdlp_plan.cpp) and the gfx950
+// fdlp_internal.h -- structures shared by the host runtime (fdlp_plan*.cpp) and the gfx950
 // kernels (fdlp_*.hip).  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>

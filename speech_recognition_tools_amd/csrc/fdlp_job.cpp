@@ -515,7 +515,7 @@ int grow_device(void** p, size_t* cap, size_t need, hipStream_t s) {
 // The samples and output rows of the largest batch each slot will hold, replaying the main loop's
 // batching over the job's entries (their sample counts from the reader): batches ramp from
 // max(64, max_frames / 32) frames, doubling up to max_frames, hold whole entries, and go round the slots
-// in turn.  Frames and rows per entry are the plan's (fdlp_plan.cpp frames_of / out_of, spectrogram mode).
+// in turn.  Frames and rows per entry are the plan's (fdlp_plan.cpp FrameGrid::frames_of / out_of, spectrogram mode).
 void slot_needs(const std::vector<int64_t>& lens, const fdlp_config& c, size_t nslots, std::vector<size_t>* smp,
                 std::vector<size_t>* rows) {
   const double ov = 1.0 - c.overlap_fraction;

@@ -687,3 +687,71 @@ def test_input_kind_table(entry, kind, pre):
         assert g.shape == w.shape, (entry, kind, pre, i, g.shape, w.shape)
         excess = np.abs(g - w) / b
         assert excess.max() <= 1.0, (entry, kind, pre, i, float(np.abs(g - w).max()))
+
+
+# One smallest batch per plan family, as (make_plan, run(plan) -> output tensor): one utterance of two analysis
+# frames for the featurisers, one utterance of tile + 1 rows (two tiles, the second of one row) for the chain plans.
+def _two_frame_pcm(frames_of):
+    T = next(t for t in range(1, 1 << 20) if frames_of(t) == 2)
+    return torch.from_numpy(np.random.RandomState(T).randint(-3000, 3000, T).astype(np.int16)).cuda(), T
+
+
+def _destroy_fdlp():
+    from speech_recognition_tools_amd import FdlpPlan, FeatureConfig, PyRandom
+    def run(plan):
+        pcm, T = _two_frame_pcm(lambda t: plan.geometry(t)[0])
+        return plan.compute(pcm, [T], PyRandom(3).randbits2(1))[0]
+    return (lambda: FdlpPlan(FeatureConfig(**KIND_FDLP), device=0, max_frames=4)), run
+
+
+def _destroy_feat(kind):
+    from speech_recognition_tools_amd.melspec import MelConfig, MelPlan
+    from speech_recognition_tools_amd.mfcc import MfccConfig, MfccPlan
+    Plan, cfg = (MelPlan, MelConfig()) if kind == "mel" else (MfccPlan, MfccConfig(context=1))
+    def run(plan):
+        pcm, T = _two_frame_pcm(plan.frames)
+        return plan.compute(pcm, [T])[0]
+    return (lambda: Plan(cfg, device=0, max_frames=4)), run
+
+
+def _destroy_chain(kind):
+    from speech_recognition_tools_amd.post import PostConfig, PostPlan, XformPlan
+    from speech_recognition_tools_amd.rnn import RnnPlan
+    cfg = PostConfig(dim=8, delta_order=2, left_context=1, right_context=1)
+    K, H, C = 8 * 3 * 3, 16, 5
+    rs = np.random.RandomState(11)
+    w = lambda *shape: (0.1 * rs.randn(*shape)).astype(np.float32)
+    if kind == "post":
+        make, tile, extra = (lambda: PostPlan(cfg, device=0)), PostPlan(cfg, device=-1).tile, ()
+    elif kind == "xform":
+        make, tile = (lambda: XformPlan(cfg, C, affine=True, device=0)), XformPlan(cfg, C, affine=True, device=-1).tile
+        extra = (torch.from_numpy(w(C, K + 1)).cuda(),)
+    else:
+        stages = [("gru", w(3 * H, K), w(3 * H, H), w(3 * H), w(3 * H)), ("linear", w(C, H), w(C))]
+        make, extra = (lambda: RnnPlan(cfg, stages, max_rows=1024, max_utts=4, device=0)), ()
+        tile = XformPlan(cfg, 3 * H, affine=True, device=-1).tile  # stage 0's chain
+    feats = torch.from_numpy(w(tile + 1, 8)).cuda()
+    return make, (lambda plan: plan.compute(feats, [tile + 1], *extra))
+
+
+DESTROY_FAMILIES = {"fdlp": _destroy_fdlp, "mel": lambda: _destroy_feat("mel"), "mfcc": lambda: _destroy_feat("mfcc"),
+                    "post": lambda: _destroy_chain("post"), "xform": lambda: _destroy_chain("xform"),
+                    "rnn": lambda: _destroy_chain("rnn")}
+
+
+def test_destroy_right_after_compute():
+    """A plan destroyed straight after its compute call, with the batch still in flight, leaves the same output as
+    one that is synchronised first: destroy waits for the device before it frees what the kernels read."""
+    for name, family in DESTROY_FAMILIES.items():
+        make, run = family()
+        outs = []
+        for sync_first in (False, True):
+            plan = make()
+            out = run(plan)
+            if sync_first:
+                torch.cuda.synchronize()
+            plan.close()
+            torch.cuda.synchronize()
+            outs.append(out.cpu())
+        assert outs[0].numel() > 0 and torch.isfinite(outs[1]).all(), name
+        assert torch.equal(outs[0], outs[1]), name

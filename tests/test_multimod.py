@@ -1,5 +1,5 @@
 """dump-multimod-outputs: the multi-stream GRU model after M chains (speech_recognition_tools_amd/multimod.py, the
-stream-batched gru_scan_kernel of csrc/fdlp_nnet.hip, fdlp_mmod_* of csrc/fdlp_plan.cpp).
+stream-batched gru_scan_kernel of csrc/fdlp_nnet.hip, fdlp_mmod_* of csrc/fdlp_plan_model.cpp).
 
 What holds the device to account, none of it fitted to what the device gives:
 
