@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define FDLP_ABI_VERSION 10
+#define FDLP_ABI_VERSION 11
 
 enum {
   FDLP_OK = 0,
@@ -281,6 +281,26 @@ int fdlp_lpc_rows(fdlp_plan* plan, const double* band_dev, int32_t n_items, doub
 /* computeModSpecFromLpc (features.py:233-246): cep [n_items, lim] from a [n_items, p+1], gg. */
 int fdlp_cepstrum_rows(fdlp_plan* plan, const double* a_dev, const double* gg_dev,
                        int32_t n_items, int32_t p, int32_t lim, double* cep_dev, void* stream);
+/* The output stage (computeFDLPSpectrogram.py:207-229; ABI 11) on the caller's envelopes: env_dev
+ * [sum_u F_u, nfilters, kk] fp64, laid out as fdlp_debug_fetch's env, utterance after utterance.  The frame
+ * and utterance tables are filled by the code fdlp_compute fills them with (utt_len, jitter and out_row as
+ * in fdlp_batch) and ola_log_tiled_kernel is launched on them; out_dev / out_f64_dev / out_q_dev /
+ * out_q_flag_dev / ark_decimals as in fdlp_batch, any of the three outputs may be NULL but not all.
+ * The refusals are fdlp_compute's: an utterance without an analysis frame, more frames than max_frames,
+ * FDLP_E_BROADCAST where the reference's OLA slicing raises, codes without ark_decimals >= 0 or a flag,
+ * a host-only or modulation-spectrum plan, more bands than an LDS tile holds (fdlp_ola_info). */
+int fdlp_ola_rows(fdlp_plan* plan, const double* env_dev, const int64_t* utt_len, int32_t n_utt,
+                  const uint8_t* jitter, const int64_t* out_row, float* out_dev, double* out_f64_dev,
+                  int16_t* out_q_dev, uint32_t* out_q_flag_dev, int32_t ark_decimals, void* stream);
+/* Launch shape of the output stage for the plan's nfilters (ABI 11; host-only plans too), from the helper
+ * the launcher itself uses:
+ *   info[0] output rows per tile (one workgroup)
+ *   info[1] the most frames overlapping a tile that the register path sums; more take the LDS loop
+ *   info[2] the most bands the register path sums; more take the LDS loop
+ *   info[3] dynamic LDS bytes of the launch
+ *   info[4] 1 when the launch needs the large-LDS function attribute (static + dynamic LDS above 64 KB)
+ *   info[5] 1 when the launcher accepts nfilters, 0 when no tile fits a CU's LDS (the launch is refused) */
+int fdlp_ola_info(const fdlp_plan* plan, int32_t info[6]);
 
 /* ---- sibling feature: mel spectrum (src/featgen/computeMelSpectrum.py, run_melspec) ----- */
 /* Replaces compute_mel_spectrum (computeMelSpectrum.py:40-170): getFrames with np.hamming(L),

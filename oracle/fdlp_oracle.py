@@ -342,6 +342,17 @@ def ola_plan(F: int, L: int, g: Geometry, jitter: Sequence[int]) -> List[Tuple[i
     return plan
 
 
+def ola_features(env: np.ndarray, T: int, jitter: Sequence[int], cfg: FdlpConfig, g: Geometry) -> np.ndarray:
+    """The last lines of FdlpOracle.utterance (computeFDLPSpectrogram.py:207-227) on given envelopes
+    [F, B, kk] of an utterance of T samples: overlap-add per ola_plan in frame order, floor, log -> [L, B]."""
+    L = n_out(T, cfg)
+    feats = np.zeros((env.shape[1], L))
+    for i, (dst, src, cnt) in enumerate(ola_plan(env.shape[0], L, g, jitter)):
+        if cnt > 0:
+            feats[:, dst:dst + cnt] += env[i, :, src:src + cnt]
+    return np.log(np.clip(feats.T, a_max=None, a_min=FLOOR))        # :227
+
+
 # --------------------------------------------------------------------------------------
 # augmentation (features.py:24-31; computeFDLPSpectrogram.py:160-166)
 # --------------------------------------------------------------------------------------

@@ -40,7 +40,7 @@ FDLP_MODE_MODSPEC_COMPLEX = 2
 FDLP_WIN_HAMMING = 0
 FDLP_WIN_HANNING = 1
 FDLP_WIN_RECT = 2
-ABI_VERSION = 10
+ABI_VERSION = 11
 FDLP_FN_LOG, FDLP_FN_EXP = 0, 1  # fdlp_device_fn
 STAGE_NAMES = ("frames_dft1", "dft2_dct", "autocorr", "lpc_env", "ola_log")
 
@@ -200,6 +200,8 @@ SIGNATURES = {
     "fdlp_dct_rows": (c_i32, [c_p, c_p, c_i32, c_p, c_p]),
     "fdlp_lpc_rows": (c_i32, [c_p, c_p, c_i32, c_p, c_p, c_p, c_p]),
     "fdlp_cepstrum_rows": (c_i32, [c_p, c_p, c_p, c_i32, c_i32, c_i32, c_p, c_p]),
+    "fdlp_ola_rows": (c_i32, [c_p, c_p, P_i64, c_i32, P_u8, P_i64, c_p, c_p, c_p, c_p, c_i32, c_p]),
+    "fdlp_ola_info": (c_i32, [c_p, P_i32]),
     "fdlp_pyrandom_create": (c_i32, [P_u32, c_i32, ctypes.POINTER(c_p)]),
     "fdlp_pyrandom_randbits2": (c_i32, [c_p, c_i64, P_u8]),
     "fdlp_pyrandom_destroy": (c_i32, [c_p]),
@@ -276,6 +278,10 @@ class FdlpError(RuntimeError):
         self.code = code
 
 
+class FdlpBroadcastError(FdlpError, ValueError):
+    """FDLP_E_BROADCAST: the reference's numpy OLA slicing raises ValueError here, and so does the binding."""
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError("libfdlp_hip.so not built (%s); run __graft_entry__.build() or "
@@ -298,7 +304,7 @@ def check(rc):
         msg = lib.fdlp_last_error()
         msg = msg.decode("utf-8", "replace") if msg else "unknown error"
         if rc == FDLP_E_BROADCAST:
-            raise ValueError(msg)
+            raise FdlpBroadcastError(rc, msg)
         raise FdlpError(rc, msg)
     return rc
 

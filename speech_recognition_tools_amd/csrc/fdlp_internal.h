@@ -213,6 +213,15 @@ hipError_t launch_cplx_modspec(const DevConsts& c, int L, const double* X, int n
 hipError_t launch_ola_log(const DevConsts& c, const double* env, const FrameDesc* frames,
                           const UttDesc* utts, int n_utt, int maxL, float* out,
                           double* out_f64, int16_t* out_q, uint32_t* q_flag, int decimals, hipStream_t s);
+// ola_log_tiled_kernel's tile shape and LDS need at B bands (no device needed; fdlp_ola_info): output rows per
+// tile, the most frames on a tile / bands its register path sums, the dynamic LDS bytes, whether those need the
+// large-LDS attribute, and whether a tile fits a CU at all.  launch_ola_log launches by the same numbers.
+struct OlaLaunch {
+  int rows, reg_frames, reg_bands;
+  size_t dyn_lds;
+  bool needs_attr, fits;
+};
+OlaLaunch ola_launch_info(int B);
 // Mel spectrum (computeMelSpectrum.py): one analysis frame and the plan constants.
 struct MelFrame {
   int64_t pcm_off, noise_off;  // noise_off < 0: no mixing

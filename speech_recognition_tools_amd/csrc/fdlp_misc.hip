@@ -36,6 +36,7 @@ __global__ __launch_bounds__(256) void ola_log_tiled_kernel(DevConsts c, const d
   const int t0 = blockIdx.x * kOlaRows;
   if (t0 >= U.L) return;
   const int nt = min(kOlaRows, U.L - t0);
+  FDLP_CHECK(u >= 0 && u < (int)gridDim.y && t0 >= 0 && nt >= 1 && nt <= kOlaRows && U.F >= 1 && U.frame0 >= 0);
   const int B = c.B, BS = c.B + 1, kk = c.kk;
   const int tid = threadIdx.x;
   for (int q = tid; q < kOlaRows * BS; q += blockDim.x) tile[q] = 0.0;
@@ -70,6 +71,8 @@ __global__ __launch_bounds__(256) void ola_log_tiled_kernel(DevConsts c, const d
       const int k = min(kf + m, U.F - 1);
       const FrameDesc fd = frames[U.frame0 + k];
       cov[m] = kf + m <= lo && t < t0 + nt && t >= fd.dst && t < fd.dst + fd.cnt;
+      FDLP_CHECK(k >= 0 && k < U.F);
+      FDLP_CHECK(!cov[m] || (fd.src + (t - fd.dst) >= 0 && fd.src + (t - fd.dst) < kk && k == kf + m && t < U.L));
       const double* er = env + (int64_t)(U.frame0 + k) * B * kk + (cov[m] ? fd.src + (t - fd.dst) : 0);
 #pragma unroll
       for (int i = 0; i < kOlaJ; ++i) {
@@ -84,6 +87,7 @@ __global__ __launch_bounds__(256) void ola_log_tiled_kernel(DevConsts c, const d
 #pragma unroll
       for (int m = 0; m < kOlaFr; ++m)
         if (cov[m]) acc = acc + v[m][i];
+      FDLP_CHECK(j >= B || (j >= 0 && tt * BS + j < kOlaRows * BS));
       if (j < B) tile[tt * BS + j] = acc;
     }
     __syncthreads();
@@ -112,6 +116,18 @@ __global__ __launch_bounds__(256) void ola_log_tiled_kernel(DevConsts c, const d
   if (bad) *qflag = 1u;
 }
 
+OlaLaunch ola_launch_info(int B) {
+  OlaLaunch o;
+  o.rows = kOlaRows;
+  o.reg_frames = kOlaFr;
+  o.reg_bands = 8 * kOlaJ;
+  o.dyn_lds = sizeof(double) * kOlaRows * (size_t)(B + 1);
+  // the kernel's static LDS (log table, frame range) counts against the same 64 KB default limit and 160 KB CU
+  constexpr size_t kStaticLds = sizeof(double) * 3 * kLogTab + 2 * sizeof(int);
+  o.needs_attr = o.dyn_lds + kStaticLds > 65536;
+  o.fits = o.dyn_lds + kStaticLds <= 160 * 1024;
+  return o;
+}
 
 hipError_t launch_ola_log(const DevConsts& c, const double* env, const FrameDesc* frames, const UttDesc* utts,
                           int n_utt, int maxL, float* out, double* out_f64, int16_t* out_q, uint32_t* q_flag,
@@ -121,12 +137,14 @@ hipError_t launch_ola_log(const DevConsts& c, const double* env, const FrameDesc
   double scale10 = 1.0;
   for (int i = 0; i < decimals; ++i) scale10 *= 10.0;
   dim3 grid((unsigned)((maxL + kOlaRows - 1) / kOlaRows), n_utt);
-  const size_t lds = sizeof(double) * kOlaRows * (size_t)(c.B + 1);
-  // the kernel's static LDS (log table, frame range) counts against the same 64 KB default limit
-  constexpr size_t kStaticLds = sizeof(double) * 3 * kLogTab + 2 * sizeof(int);
-  if (lds + kStaticLds > 160 * 1024) return hipErrorInvalidValue;  // B > ~620 bands: no tile fits a CU
-  if (lds + kStaticLds > 65536)
-    (void)hipFuncSetAttribute((const void*)ola_log_tiled_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  const OlaLaunch o = ola_launch_info(c.B);
+  const size_t lds = o.dyn_lds;
+  if (!o.fits) return hipErrorInvalidValue;  // B > 630 bands: no tile fits a CU
+  if (o.needs_attr) {
+    const hipError_t e =
+        hipFuncSetAttribute((const void*)ola_log_tiled_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
   hipLaunchKernelGGL(ola_log_tiled_kernel, grid, dim3(256), lds, s, c, env, frames, utts, out, out_f64, out_q, q_flag,
                      decimals, scale10);
   (void)kmark(kKOlaLog, s);

@@ -162,6 +162,53 @@ int64_t out_of(const fdlp_plan* p, int64_t T) {
   return (int64_t)ceil((double)(T * (int64_t)p->cfg.frate) / (double)p->cfg.srate);
 }
 
+// The descriptor tables of a batch into the plan's staging arrays (frames.host, utts.host): per utterance the
+// frame count, the OLA slices (ola_table, F - 1 jitter draws each) and the output rows.  One function behind
+// fdlp_compute and fdlp_ola_rows, so the stage entry point publishes what the pipeline publishes.  pcm_off is
+// null where no samples are read (fdlp_ola_rows), noise_off null without noise mixing.
+int fill_batch_tables(fdlp_plan* p, int n_utt, const int64_t* utt_len, const int64_t* out_row, const uint8_t* jit,
+                      const int64_t* pcm_off, const int64_t* noise_off, const double* noise_alpha, int64_t* nf_out,
+                      int* maxL_out) {
+  int64_t nf = 0;
+  int maxL = 0;
+  std::vector<int32_t> dst, src, cnt;
+  for (int u = 0; u < n_utt; ++u) {
+    const int64_t T = utt_len[u];
+    const int64_t F = p->grid.frames_of(T), L = out_of(p, T);
+    if (F < 1) return fail(FDLP_E_INVALID, "utterance too short: no analysis frame (scipy dct of an empty array)");
+    if (L > INT32_MAX / 2) return fail(FDLP_E_INVALID, "utterance too long");
+    if (nf + F > p->max_frames) return fail(FDLP_E_CAPACITY, "batch exceeds the plan's max_frames");
+    if (noise_off && noise_off[u] < 0) return fail(FDLP_E_INVALID, "negative noise offset");
+    dst.assign(F, 0); src.assign(F, 0); cnt.assign(F, 0);
+    if (!p->modspec) {
+      const int rc = ola_table(p->kk, p->kkb2, p->ola_hop, (int)F, (int)L, jit, dst.data(), src.data(), cnt.data());
+      if (rc != FDLP_OK) return rc;
+      if (jit) jit += F - 1;
+    }
+    for (int64_t k = 0; k < F; ++k) {
+      fdlp::FrameDesc& fd = p->frames.host[nf + k];
+      fd.pcm_off = pcm_off ? pcm_off[u] : 0;
+      fd.noise_off = noise_off ? noise_off[u] : -1;
+      fd.alpha = noise_off ? noise_alpha[u] : 0.0;
+      fd.T = (int32_t)T;
+      fd.k = (int32_t)k;
+      fd.dst = dst[k]; fd.src = src[k]; fd.cnt = cnt[k];
+      fd.utt = u;
+    }
+    fdlp::UttDesc& ud = p->utts.host[u];
+    ud.out_row = out_row[u];
+    ud.L = (int32_t)L;
+    ud.frame0 = (int32_t)nf;
+    ud.F = (int32_t)F;
+    ud.pad = 0;
+    maxL = std::max(maxL, (int)L);
+    nf += F;
+  }
+  *nf_out = nf;
+  *maxL_out = maxL;
+  return FDLP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -546,40 +593,9 @@ int fdlp_compute(fdlp_plan* p, const fdlp_batch* b, void* stream) {
   if ((rc = p->utts.wait()) != FDLP_OK) return rc;
   int64_t nf = 0;
   int maxL = 0;
-  const uint8_t* jit = b->jitter;
-  std::vector<int32_t> dst, src, cnt;
-  for (int u = 0; u < b->n_utt; ++u) {
-    const int64_t T = b->utt_len[u];
-    const int64_t F = p->grid.frames_of(T), L = out_of(p, T);
-    if (F < 1) return fail(FDLP_E_INVALID, "utterance too short: no analysis frame (scipy dct of an empty array)");
-    if (L > INT32_MAX / 2) return fail(FDLP_E_INVALID, "utterance too long");
-    if (nf + F > p->max_frames) return fail(FDLP_E_CAPACITY, "batch exceeds the plan's max_frames");
-    if (b->noise_dev && b->noise_off[u] < 0) return fail(FDLP_E_INVALID, "negative noise offset");
-    dst.assign(F, 0); src.assign(F, 0); cnt.assign(F, 0);
-    if (!p->modspec) {
-      rc = ola_table(p->kk, p->kkb2, p->ola_hop, (int)F, (int)L, jit, dst.data(), src.data(), cnt.data());
-      if (rc != FDLP_OK) return rc;
-      if (jit) jit += F - 1;
-    }
-    for (int64_t k = 0; k < F; ++k) {
-      fdlp::FrameDesc& fd = p->frames.host[nf + k];
-      fd.pcm_off = b->pcm_off[u];
-      fd.noise_off = b->noise_dev ? b->noise_off[u] : -1;
-      fd.alpha = b->noise_dev ? b->noise_alpha[u] : 0.0;
-      fd.T = (int32_t)T;
-      fd.k = (int32_t)k;
-      fd.dst = dst[k]; fd.src = src[k]; fd.cnt = cnt[k];
-      fd.utt = u;
-    }
-    fdlp::UttDesc& ud = p->utts.host[u];
-    ud.out_row = b->out_row[u];
-    ud.L = (int32_t)L;
-    ud.frame0 = (int32_t)nf;
-    ud.F = (int32_t)F;
-    ud.pad = 0;
-    maxL = std::max(maxL, (int)L);
-    nf += F;
-  }
+  if ((rc = fill_batch_tables(p, b->n_utt, b->utt_len, b->out_row, b->jitter, b->pcm_off,
+                              b->noise_dev ? b->noise_off : nullptr, b->noise_alpha, &nf, &maxL)) != FDLP_OK)
+    return rc;
   p->last_frames = (int)nf;
   if (nf == 0) return FDLP_OK;
   // Sub-batches alternate between the caller's stream and the plan's second stream so that the
@@ -1007,6 +1023,42 @@ int fdlp_cepstrum_rows(fdlp_plan* p, const double* a, const double* gg, int32_t 
                        double* cep, void* stream) {
   if (!p || !a || !gg || !cep || n < 0 || order < 1 || lim < 2) return fail(FDLP_E_INVALID, "fdlp_cepstrum_rows: bad args");
   HIP_TRY(fdlp::launch_cepstrum(order, lim, a, gg, n, cep, (hipStream_t)stream));
+  return FDLP_OK;
+}
+
+int fdlp_ola_rows(fdlp_plan* p, const double* env, const int64_t* utt_len, int32_t n_utt, const uint8_t* jitter,
+                  const int64_t* out_row, float* out, double* out_f64, int16_t* out_q, uint32_t* out_q_flag,
+                  int32_t ark_decimals, void* stream) {
+  if (!p) return fail(FDLP_E_INVALID, "fdlp_ola_rows: null plan");
+  if (n_utt < 0 || (n_utt > 0 && (!env || !utt_len || !out_row)))
+    return fail(FDLP_E_INVALID, "fdlp_ola_rows: missing batch arrays");
+  if (!out && !out_f64 && !out_q) return fail(FDLP_E_INVALID, "fdlp_ola_rows: no output buffer");
+  if (p->modspec) return fail(FDLP_E_INVALID, "fdlp_ola_rows: modulation-spectrum plan (no envelope / OLA stage)");
+  if (out_q && (ark_decimals < 0 || !out_q_flag))
+    return fail(FDLP_E_INVALID, "fdlp_ola_rows: out_q_dev needs ark_decimals >= 0 and out_q_flag_dev");
+  if (p->device < 0) return fail(FDLP_E_INVALID, "fdlp_ola_rows: host-only plan (created with device < 0)");
+  hipStream_t s = (hipStream_t)stream;
+  DeviceGuard dg(p->device);
+  HIP_TRY(dg.status());
+  int rc;
+  if ((rc = p->utts.wait()) != FDLP_OK) return rc;  // the staging tables may still feed the previous call's copies
+  int64_t nf = 0;
+  int maxL = 0;
+  if ((rc = fill_batch_tables(p, n_utt, utt_len, out_row, jitter, nullptr, nullptr, nullptr, &nf, &maxL)) != FDLP_OK)
+    return rc;
+  if (nf == 0) return FDLP_OK;
+  if ((rc = p->frames.publish((size_t)nf, s)) != FDLP_OK) return rc;
+  if ((rc = p->utts.publish((size_t)n_utt, s)) != FDLP_OK) return rc;
+  HIP_TRY(fdlp::launch_ola_log(p->dc, env, p->frames.dev, p->utts.dev, n_utt, maxL, out, out_f64, out_q, out_q_flag,
+                               ark_decimals, s));
+  return FDLP_OK;
+}
+
+int fdlp_ola_info(const fdlp_plan* p, int32_t info[6]) {
+  if (!p || !info) return fail(FDLP_E_INVALID, "fdlp_ola_info: need a plan and info[6]");
+  const fdlp::OlaLaunch o = fdlp::ola_launch_info(p->B);
+  info[0] = o.rows; info[1] = o.reg_frames; info[2] = o.reg_bands;
+  info[3] = (int32_t)std::min<size_t>(o.dyn_lds, INT32_MAX); info[4] = o.needs_attr ? 1 : 0; info[5] = o.fits ? 1 : 0;
   return FDLP_OK;
 }
 

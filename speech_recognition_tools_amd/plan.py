@@ -313,6 +313,73 @@ class FdlpPlan:
                                      s.cuda_stream))
         return cep
 
+    def ola_info(self) -> dict:
+        """Launch shape of the output stage for this plan's band count (fdlp_ola_info; also on a host-only
+        plan): ``rows`` per tile, the register path's ``reg_frames`` / ``reg_bands`` limits (a tile with more
+        frames on it, or a plan with more bands, takes the LDS loop), the launch's dynamic ``lds_bytes``,
+        whether it ``needs_attr`` (the large-LDS function attribute) and whether the launcher ``accepted`` it."""
+        v = (_lib.c_i32 * 6)()
+        check(lib.fdlp_ola_info(self._h, v))
+        return dict(rows=int(v[0]), reg_frames=int(v[1]), reg_bands=int(v[2]), lds_bytes=int(v[3]),
+                    needs_attr=bool(v[4]), accepted=bool(v[5]))
+
+    def ola_rows(self, env: torch.Tensor, lengths: Sequence[int], jitter: Optional[np.ndarray],
+                 out_rows: Optional[Sequence[int]] = None, ark_decimals: int = 3, want_f64: bool = True,
+                 out: Optional[torch.Tensor] = None, out_q: Optional[torch.Tensor] = None,
+                 q_flag: Optional[torch.Tensor] = None, out_f64: Optional[torch.Tensor] = None):
+        """The output stage (OLA, floor, log, rounding / codes) on given envelopes (fdlp_ola_rows): ``env``
+        fp64 [sum F, B, kk] on the device, laid out as debug_fetch's, for utterances of ``lengths`` samples
+        with ``jitter`` as in compute.  ``out_rows`` places each utterance's first row (default: one after
+        the other).  ``out`` / ``out_f64`` / ``out_q`` are written in place where given; without ``out`` and
+        ``out_q`` a float32 buffer is allocated, and with ``want_f64`` an fp64 one.
+
+        Returns (feats float32 or None, first rows int64 [n_utt], feats_f64 or None); the buffers cover
+        max(out_rows + L) rows."""
+        if not env.is_cuda or env.dtype != torch.float64 or env.dim() != 3 or not env.is_contiguous():
+            raise ValueError("env must be a contiguous float64 device tensor [sum F, B, kk]")
+        lens = np.ascontiguousarray(np.asarray(lengths, dtype=np.int64))
+        n = lens.size
+        geo = [self.geometry(int(T)) for T in lens]
+        nf = sum(F for F, _ in geo)
+        if env.shape[0] < nf or env.shape[1] != self.B or env.shape[2] != self.kk:
+            raise ValueError("env must hold [sum F = %d, B = %d, kk = %d] values" % (nf, self.B, self.kk))
+        Ls = np.array([L for _, L in geo], dtype=np.int64)
+        if out_rows is None:
+            rows = np.zeros(n, dtype=np.int64)
+            if n:
+                rows[1:] = np.cumsum(Ls)[:-1]
+        else:
+            rows = np.ascontiguousarray(np.asarray(out_rows, dtype=np.int64))
+            if rows.size != n or (n and int(rows.min()) < 0):
+                raise ValueError("out_rows must hold one non-negative first row per utterance")
+        total = int((rows + Ls).max()) if n else 0
+        dev = env.device
+        D = self.B
+        mk = torch.empty if out_rows is None else torch.zeros
+        if out is None and out_q is None:
+            out = mk((total, D), dtype=torch.float32, device=dev)
+        if out_f64 is None and want_f64:
+            out_f64 = mk((total, D), dtype=torch.float64, device=dev)
+        for t, dt, name in ((out, torch.float32, "out"), (out_f64, torch.float64, "out_f64"),
+                            (out_q, torch.int16, "out_q")):
+            if t is not None and (t.dtype != dt or t.dim() != 2 or t.shape[0] < total or t.shape[1] != D
+                                  or not t.is_contiguous()):
+                raise ValueError("%s must be a contiguous %s [>= %d, %d] tensor" % (name, dt, total, D))
+        if out_q is not None and q_flag is not None and (q_flag.dtype != torch.int32 or q_flag.numel() < 1):
+            raise ValueError("q_flag must be an int32 tensor of at least one element")
+        need = sum(max(F - 1, 0) for F, _ in geo)
+        jit = np.ascontiguousarray(np.zeros(max(need, 1)) if jitter is None else jitter, dtype=np.uint8)
+        if jit.size < need:
+            raise ValueError("need F-1 jitter draws per utterance")
+        s = torch.cuda.current_stream(dev)
+        check(lib.fdlp_ola_rows(self._h, env.data_ptr(), ptr(lens, ctypes.c_int64), n, ptr(jit, ctypes.c_uint8),
+                                ptr(rows, ctypes.c_int64), _dev_ptr(out, "out") if out is not None else None,
+                                out_f64.data_ptr() if out_f64 is not None else None,
+                                _dev_ptr(out_q, "out_q") if out_q is not None else None,
+                                _dev_ptr(q_flag, "q_flag") if q_flag is not None else None,
+                                int(ark_decimals), s.cuda_stream))
+        return out, rows, out_f64
+
 
 def _dev_ptr(t: torch.Tensor, name: str) -> int:
     """Device address of a device tensor, or of a pinned host tensor through its device mapping (the

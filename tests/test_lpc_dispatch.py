@@ -23,8 +23,9 @@ H = env_nfft / 2).  DISPATCH_CASES below holds one small batch per reachable ins
 
 `python tests/test_lpc_dispatch.py --record` (on the device) rewrites tests/data/lpc_dispatch_errors.jsonl,
 the per-row maxima next to their bars.  MEASURED_WORST below quotes the worst error / bar ratios of that file:
-0.0023 on r (row 36, 'lds'), 0.00046 on gg and 0.00041 on a (row 38, 'lattice8'), 0.00012 on the features and
-on log env and 0.00006 on the cepstra (row 00, 'lds'); test_recorded_errors_match_docstring keeps the two equal.
+0.25 on r (row 55, 247 mel bands of one to three taps), 0.00052 on gg (row 42, 'lattice8'), 0.00049 on a (row 53),
+0.00012 on the features and on log env and 0.00006 on the cepstra (row 00, 'lds');
+test_recorded_errors_match_docstring keeps the two equal.
 """
 import functools
 import json
@@ -56,12 +57,14 @@ CHECKS_LIB = os.path.join(ROOT, "speech_recognition_tools_amd", "lib", "libfdlp_
 # Worst error / bar ratio per quantity over tests/data/lpc_dispatch_errors.jsonl (all rows, all paths), as
 # (ratio, row, path): filled from the recorded file, test_recorded_errors_match_docstring compares them.
 # Every path of every row is three to four orders of magnitude inside its bar (largest absolute errors:
-# a 4.1e-13, gg 4.6e-15, cep 4.2e-13, log env 3.7e-12, features 3.1e-12 against feature bars of 4.3e-11 ..
-# 4.8e-7; the float32 rows equal the rounded oracle's), so no margin was widened and no kernel changed.
+# a 4.9e-13, gg 5.2e-15, cep 2.4e-13, log env 2.7e-12, features 2.0e-12 against feature bars of 4.3e-11 ..
+# 4.8e-7; the float32 rows equal the rounded oracle's), so no margin was widened and no kernel changed.  The one
+# exception is r of row 55 (247 mel bands at N = 1600, one to three taps each): 2.5e-13 r0, a quarter of the
+# suite's 1e-12 bar on the device autocorrelation; its a, gg, cepstra and features are as far inside as the rest.
 MEASURED_WORST = {
-    "a": (0.000412, "38-cochlear-fd1-fr160-p150-M100-spectrogram", "lattice8"),
-    "gg": (0.000456, "38-cochlear-fd1-fr160-p150-M100-spectrogram", "lattice8"),
-    "r": (0.00226, "36-cochlear-fd0.1-fr100-p40-M15-spectrogram", "lds"),
+    "a": (0.000494, "53-mel-fd0.1-fr100-p20-M15-spectrogram", "auto"),
+    "gg": (0.000521, "42-cochlear-fd1.5-fr100-p150-M300-spectrogram", "lattice8"),
+    "r": (0.248, "55-mel-fd0.1-fr100-p12-M10-spectrogram", "auto"),
     "cep": (6.24e-05, "00-cochlear-fd0.5-fr100-p1-M20-spectrogram", "lds"),
     "env": (0.000117, "00-cochlear-fd0.5-fr100-p1-M20-spectrogram", "lds"),
     "feat": (0.000123, "00-cochlear-fd0.5-fr100-p1-M20-spectrogram", "lds"),
@@ -142,6 +145,11 @@ DISPATCH_CASES = [
     _mod(MEL, 65, 70, 1, mode="modspec_complex"),
     _mod(MEL, 129, 130, 5, mode="modspec_complex", absolute_value=True),
     _mod(MEL, 238, 260, 1, mode="modspec_complex"),
+    # ---- more than 80 bands: the output stage's LDS loop behind the whole pipeline (tests/test_ola_stage.py
+    # holds that stage alone); 247 bands is the first count whose launch needs the large-LDS attribute ----
+    (MEL, 81, 0.1, 100, 20, 15, "spectrogram"),
+    (COCH, 81, 0.5, 100, 30, 30, "spectrogram"),
+    (MEL, 247, 0.1, 100, 12, 10, "spectrogram"),
 ]
 ROW_IDS = ["%02d-%s-fd%g-fr%d-p%d-M%d-%s" % (i, r[0].split(",")[0], r[2], r[3], r[4], r[5], r[6])
            for i, r in enumerate(DISPATCH_CASES)]
@@ -318,16 +326,6 @@ def perturbed(r, seed):
     return r + s * rng.standard_normal(r.shape)
 
 
-def ola_features(orc, env, T, jit):
-    """The last lines of FdlpOracle.utterance (computeFDLPSpectrogram.py:207-227) on given envelopes."""
-    L = O.n_out(T, orc.cfg)
-    feats = np.zeros((orc.cfg.nfilters, L))
-    for i, (dst, src, cnt) in enumerate(O.ola_plan(env.shape[0], L, orc.g, jit)):
-        if cnt > 0:
-            feats[:, dst:dst + cnt] += env[i, :, src:src + cnt]
-    return np.log(np.clip(feats.T, a_max=None, a_min=O.FLOOR))
-
-
 def log_env(env):
     return np.log(env[..., 1:-1])
 
@@ -363,7 +361,7 @@ def spectro_reference(idx):
         feats, f0 = [], 0
         for x, k, jit in zip(sigs, keeps, jits):
             F = k.r.shape[0]
-            feats.append(ola_features(orc, env[f0 * B:(f0 + F) * B].reshape(F, B, -1), x.size, jit))
+            feats.append(O.ola_features(env[f0 * B:(f0 + F) * B].reshape(F, B, -1), x.size, jit, orc.cfg, orc.g))
             f0 += F
         return cep, env, feats
 
