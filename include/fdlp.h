@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define FDLP_ABI_VERSION 11
+#define FDLP_ABI_VERSION 12
 
 enum {
   FDLP_OK = 0,
@@ -179,6 +179,20 @@ int fdlp_device_checks(int32_t* enabled, uint32_t* violations, uint32_t* last_li
 #define FDLP_AC_STRUCTURED_MFMA 3
 int fdlp_set_autocorr_path(fdlp_plan* plan, int32_t path);
 int fdlp_autocorr_path(const fdlp_plan* plan);
+/* What the autocorrelation stage launches for a requested path (ABI 12): FDLP_AC_AUTO or one of the explicit
+ * paths, resolved as fdlp_set_autocorr_path resolves it (FDLP_E_INVALID likewise) without changing the plan's
+ * path.  Answered by the functions the launchers themselves dispatch by; works on a host-only plan.
+ *   out[0] the path launched: FDLP_AC_DIRECT, FDLP_AC_STRUCTURED or FDLP_AC_STRUCTURED_MFMA
+ *   out[1] lag tiles NT of autocorr_kernel / ac_sweep_kernel / ac_band_kernel<NT>
+ * and, on FDLP_AC_STRUCTURED (0 on the other two paths, which launch none of these):
+ *   out[2] lags per lane A of ac_vsweep_kernel<A, C> (4, 8 or 10)
+ *   out[3] chains the flat tops need, out[4] the chain slots C instantiated for them (4, 5, 6 or 8)
+ *   out[5] position parts of the flat sweep (1 or 2)
+ *   out[6], out[7] 1 when the skirt sweeps <A, 0> / the flat sweep <A, C> take their plain runs in the 2x2
+ *          fast-correlation form
+ *   out[8] 1 when ac_wrap_kernel runs (bands whose outermost lags - 1 taps are skirt taps share one wrap straddle)
+ *   out[9] bands whose straddles ac_band_kernel stages in its compact `fast` form (the others: the general form) */
+int fdlp_plan_autocorr_dispatch(const fdlp_plan* plan, int32_t path, int32_t out[10]);
 /* LPC stage (Levinson-Durbin + cepstrum + envelope).  FDLP_LPC_AUTO (plan default): the register-resident
  * lattice kernels (durbin4_kernel, 4 lanes per item, for 128 <= p <= 150; durbin8_kernel, 8 lanes per item,
  * for 150 < p <= 183; then the cepstrum / envelope kernel); FDLP_LPC_LATTICE8 (ABI 6): the same with

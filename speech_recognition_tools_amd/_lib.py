@@ -40,7 +40,7 @@ FDLP_MODE_MODSPEC_COMPLEX = 2
 FDLP_WIN_HAMMING = 0
 FDLP_WIN_HANNING = 1
 FDLP_WIN_RECT = 2
-ABI_VERSION = 11
+ABI_VERSION = 12
 FDLP_FN_LOG, FDLP_FN_EXP = 0, 1  # fdlp_device_fn
 STAGE_NAMES = ("frames_dft1", "dft2_dct", "autocorr", "lpc_env", "ola_log")
 
@@ -189,6 +189,7 @@ SIGNATURES = {
     "fdlp_plan_sweep_schedule": (c_i32, [c_p, c_i32, c_i32, c_p, c_p, c_p, c_i32]),
     "fdlp_set_lpc_path": (c_i32, [c_p, c_i32]),
     "fdlp_plan_lpc_dispatch": (c_i32, [c_p, P_i32]),
+    "fdlp_plan_autocorr_dispatch": (c_i32, [c_p, c_i32, P_i32]),
     "fdlp_device_checks": (c_i32, [c_p, c_p, c_p, c_i32]),
     "fdlp_set_dct_path": (c_i32, [c_p, c_i32]),
     "fdlp_dct_path": (c_i32, [c_p]),

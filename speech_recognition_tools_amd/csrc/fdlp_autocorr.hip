@@ -381,6 +381,28 @@ __global__ __launch_bounds__(64, 2) void ac_sweep_kernel(DevConsts c, const doub
   while (k < B) snapshot();
 }
 
+// ac_band_kernel<NT, VS>'s straddle geometry and the condition of its `fast` staging, in one place for the
+// kernel and for the host's account of the dispatch (autocorr_dispatch_info): the A window of a straddle
+// (>= nlags - 1), the 64-position steps staged per boundary, whether two compact boundary regions fit the LDS.
+constexpr int kAcBandEpi = (32 + 31) * 17;  // diag_blocks<NT, 32> image
+constexpr int kAcBandLds = 2 * kAcRing > kAcBandEpi ? 2 * kAcRing : kAcBandEpi;
+__host__ __device__ constexpr int ac_band_win(int nt) { return (16 * nt + 63) / 64 * 64; }
+__host__ __device__ constexpr int ac_band_steps(int nt) { return (ac_band_win(nt) + 16 * nt + 63) / 64; }
+__host__ __device__ constexpr bool ac_band_fits(int nt) { return 2 * (ac_band_win(nt) + 64 + 16 * nt) <= kAcBandLds; }
+// The condition itself, kw being the band's shared-wrap factor (0: its wrap straddle comes from the taps, or no
+// ac_wrap_kernel ran).  One expression for the kernel, which needs it written out in place over its own
+// constants (through a function it compiles to the same tests in another block layout), and for the host's
+// ac_band_fast.
+#ifdef FDLP_AB_BAND_GENERIC  // A/B build: every band through the general staging
+#define FDLP_AC_BAND_FAST(fits, vs, win, steps, kw, m1, m2, nlags, N) false
+#else
+#define FDLP_AC_BAND_FAST(fits, vs, win, steps, kw, m1, m2, nlags, N) \
+  ((fits) && (vs) && (kw) != 0.0 && (m1) >= (win) && (m2) - (m1) >= (nlags) - 1 && (m2) + ((steps) * 64 - (win)) <= (N))
+#endif
+static bool ac_band_fast(int nt, bool vs, double kw, int m1, int m2, int nlags, int N) {
+  return FDLP_AC_BAND_FAST(ac_band_fits(nt), vs, ac_band_win(nt), ac_band_steps(nt), kw, m1, m2, nlags, N);
+}
+
 // Per (frame, band): flat-top pairs (unit taps on [m1, m2)), the pairs straddling m1, m2 and the
 // circular wrap at N (true taps W_j D), plus the two skirt snapshots from ac_sweep_kernel:
 //   r_j[l] = K_j R_y(N-m1_j)[l] + flat + straddles + K'_j R_z(m2_j)[l]
@@ -394,9 +416,9 @@ __global__ __launch_bounds__(64, 4) void ac_band_kernel(DevConsts c, const doubl
                                                         const double* __restrict__ rpart,
                                                         const double* __restrict__ rwrap, int items) {
   static_assert(16 * NT <= kAcChunk, "window halo must fit one chunk");
-  constexpr int kEpi = (32 + 31) * 17;                   // diag_blocks<NT, 32> image
-  constexpr int kWin = (16 * NT + 63) / 64 * 64;         // A window of a straddle (>= nlags - 1)
-  constexpr int kLds = 2 * kAcRing > kEpi ? 2 * kAcRing : kEpi;
+  constexpr int kEpi = kAcBandEpi;                       // diag_blocks<NT, 32> image
+  constexpr int kWin = ac_band_win(NT);                  // A window of a straddle (>= nlags - 1)
+  constexpr int kLds = kAcBandLds;
   static_assert(kEpi <= kLds && 2 * kWin + 16 * NT <= kLds, "LDS regions");
   __shared__ double xs[kLds];
 
@@ -462,7 +484,7 @@ __global__ __launch_bounds__(64, 4) void ac_band_kernel(DevConsts c, const doubl
 
   // straddles: A = x[m], m in [lb, b) (the region just below boundary b, at most nlags-1 long),
   // B = x[(m + l) mod N] for m + l >= b, x = W_j D
-  constexpr int kSt = (kWin + 16 * NT + 63) / 64;  // B reads reach xb[kWin - 1 + 16 NT - 1]
+  constexpr int kSt = ac_band_steps(NT);  // B reads reach xb[kWin - 1 + 16 NT - 1]
   static_assert(kSt > kWin / 64 && kWin % 64 == 0, "window layout");
   // the MFMAs of one straddle from its staged windows xa / xb (B reads xb[kWin - 63, kWin + 16 NT))
   auto straddle = [&](const double* xa, const double* xb, int st0) {
@@ -494,12 +516,9 @@ __global__ __launch_bounds__(64, 4) void ac_band_kernel(DevConsts c, const doubl
   // into two compact LDS regions [A: kWin | zeros: 64 | B: 16 NT], so an item waits for memory once before
   // its straddles instead of once per boundary.
   constexpr int kReg = kWin + 64 + 16 * NT;  // one boundary's compact region
-  constexpr bool kFits = 2 * kReg <= kLds;   // every order up to p = 190 (NT <= 12)
-#ifdef FDLP_AB_BAND_GENERIC  // A/B build: every band through the general staging
-  const bool fast = false;
-#else
-  const bool fast = kFits && VS && kw != 0.0 && m1 >= kWin && m2 - m1 >= nlags - 1 && m2 + (kSt * 64 - kWin) <= N;
-#endif
+  constexpr bool kFits = ac_band_fits(NT);   // every order up to p = 190 (NT <= 12)
+  static_assert(kFits == (2 * kReg <= kLds), "ac_band_fits is the two compact regions");
+  const bool fast = FDLP_AC_BAND_FAST(kFits, VS, kWin, kSt, kw, m1, m2, nlags, N);
   if constexpr (kFits) if (fast) {
     constexpr int kA = kWin / 64, kB = kSt - kWin / 64;  // staged A / B slots
     static_assert(kB <= kA + 1, "m2 B taps");
@@ -1286,6 +1305,27 @@ int vsweep_chains(int C) {
   return 0;
 }
 
+// vs_fast22<A, C>() for run-time A, C (C = 0: the skirt sweeps), the template itself behind two switches
+template <int A>
+static bool vs_fast22_chains(int C) {
+  switch (C) {
+    case 0: return vs_fast22<A, 0>();
+    case 4: return vs_fast22<A, 4>();
+    case 5: return vs_fast22<A, 5>();
+    case 6: return vs_fast22<A, 6>();
+    case 8: return vs_fast22<A, 8>();
+    default: return false;
+  }
+}
+bool vsweep_fast22(int A, int C) {
+  switch (A) {
+    case 4: return vs_fast22_chains<4>(C);
+    case 8: return vs_fast22_chains<8>(C);
+    case 10: return vs_fast22_chains<10>(C);
+    default: return false;
+  }
+}
+
 template <int A, int C>
 static hipError_t launch_vsweep_ac(const DevConsts& c, const double* dct, int nframes, double* r, double* rup,
                                    double* rflat, double* rpart, hipStream_t s) {
@@ -1319,13 +1359,17 @@ static hipError_t launch_vsweep(const DevConsts& c, const double* dct, int nfram
   }
 }
 
+// ac_wrap_kernel runs (and ac_band_kernel takes the shared wrap straddle) when the plan has the per-band
+// factors and the Wrap rows, and the lags fit the kernel's LDS edges
+static bool ac_wrap_shared(bool have_rows, int nlags) { return have_rows && nlags <= kMaxWrapLags; }
+
 template <int NT>
 static hipError_t launch_struct_nt(const DevConsts& c, const double* dct, int nframes, double* r, double* rup,
                                    double* rflat, double* rpart, double* rwrap, hipStream_t s) {
   if (rflat) {  // lag-parallel VALU sweeps (flat tops included) + straddles
     const hipError_t e = launch_vsweep(c, dct, nframes, r, rup, rflat, rpart, s);
     if (e != hipSuccess) return e;
-    const bool wrap = rwrap && c.sk_wrap && c.nlags <= kMaxWrapLags;
+    const bool wrap = ac_wrap_shared(rwrap && c.sk_wrap, c.nlags);
     if (wrap) {
       hipLaunchKernelGGL(ac_wrap_kernel, dim3(nframes), dim3(64), 0, s, c, dct, rwrap, nframes);
       (void)kmark(kKAcWrap, s);
@@ -1358,6 +1402,27 @@ hipError_t launch_autocorr_structured(const DevConsts& c, const double* dct, int
 #undef FDLP_ST_CASE
     default: return hipErrorInvalidValue;
   }
+}
+
+// What the autocorrelation stage launches on `path` (FDLP_AC_* of fdlp.h, already resolved: 1 direct,
+// 2 structured, 3 structured_mfma), from the functions the launchers above call; needs no device.
+void autocorr_dispatch_info(int path, int N, int nlags, int B, int fl_C, int fl_H, const int2* reg,
+                            const double* wrap_kw, int32_t out[10]) {
+  for (int k = 0; k < 10; ++k) out[k] = 0;
+  out[0] = path;
+  out[1] = autocorr_tiles(nlags);
+  if (path != 2) return;  // only the structured path launches ac_vsweep_kernel, ac_wrap_kernel and the VS band kernel
+  const int A = vsweep_lanes_lags(nlags), slots = vsweep_chains(fl_C);
+  out[2] = A;
+  out[3] = fl_C;
+  out[4] = slots;
+  out[5] = fl_H;
+  out[6] = vsweep_fast22(A, 0) ? 1 : 0;
+  out[7] = vsweep_fast22(A, slots) ? 1 : 0;
+  const bool wrap = ac_wrap_shared(wrap_kw != nullptr, nlags);
+  out[8] = wrap ? 1 : 0;
+  for (int j = 0; j < B; ++j)
+    out[9] += ac_band_fast(out[1], true, wrap ? wrap_kw[j] : 0.0, reg[j].x, reg[j].y, nlags, N) ? 1 : 0;
 }
 
 hipError_t checks_autocorr(unsigned int* v, bool reset) { return fdlp_checks_local(v, reset); }

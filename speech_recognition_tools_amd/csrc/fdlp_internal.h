@@ -185,6 +185,12 @@ hipError_t launch_autocorr_structured(const DevConsts& c, const double* dct, int
                                       double* rup, double* rflat, double* rflat_part, double* rwrap, hipStream_t s);
 int vsweep_lanes_lags(int nlags);   // lags per lane of ac_vsweep_kernel, 0 = unsupported
 int vsweep_chains(int C);           // chain count instantiated for C needed chains, 0 = unsupported
+bool vsweep_fast22(int A, int C);   // vs_fast22<A, C>(): the sweep's plain runs in the 2x2 fast-correlation form (C = 0: skirts)
+// What the autocorrelation stage launches on the resolved path (1 direct, 2 structured, 3 structured_mfma), from
+// the launchers' own dispatch functions (no device needed): out as fdlp_plan_autocorr_dispatch documents it.
+// reg [B] (m1, m2); wrap_kw [B] the shared-wrap factors, null when the plan has none.
+void autocorr_dispatch_info(int path, int N, int nlags, int B, int fl_C, int fl_H, const int2* reg,
+                            const double* wrap_kw, int32_t out[10]);
 hipError_t launch_levinson(const DevConsts& c, const double* r, int items, double* a,
                            double* gg, hipStream_t s);
 hipError_t launch_cepstrum(int p, int M, const double* a, const double* gg, int items,

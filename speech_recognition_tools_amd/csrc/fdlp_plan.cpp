@@ -723,19 +723,35 @@ int fdlp_compute(fdlp_plan* p, const fdlp_batch* b, void* stream) {
   return FDLP_OK;
 }
 
-int fdlp_set_autocorr_path(fdlp_plan* p, int32_t path) {
-  if (!p) return fail(FDLP_E_INVALID, "fdlp_set_autocorr_path: null plan");
-  if (path == FDLP_AC_AUTO) {
-    p->ac_path = !p->sk_avail ? FDLP_AC_DIRECT : (p->vs_avail ? FDLP_AC_STRUCTURED : FDLP_AC_STRUCTURED_MFMA);
-  } else if (path == FDLP_AC_DIRECT) {
-    p->ac_path = FDLP_AC_DIRECT;
-  } else if (path == FDLP_AC_STRUCTURED || path == FDLP_AC_STRUCTURED_MFMA) {
+// The path a request launches (fdlp_set_autocorr_path, fdlp_plan_autocorr_dispatch): FDLP_AC_DIRECT,
+// FDLP_AC_STRUCTURED or FDLP_AC_STRUCTURED_MFMA, or a failure code.
+static int resolve_autocorr_path(const fdlp_plan* p, int32_t path, const char* who) {
+  if (path == FDLP_AC_AUTO)
+    return !p->sk_avail ? FDLP_AC_DIRECT : (p->vs_avail ? FDLP_AC_STRUCTURED : FDLP_AC_STRUCTURED_MFMA);
+  if (path == FDLP_AC_DIRECT) return FDLP_AC_DIRECT;
+  if (path == FDLP_AC_STRUCTURED || path == FDLP_AC_STRUCTURED_MFMA) {
     if (!p->sk_avail)
       return fail(FDLP_E_INVALID, "structured autocorrelation needs the cochlear filterbank with fixed=1");
-    p->ac_path = (path == FDLP_AC_STRUCTURED && p->vs_avail) ? FDLP_AC_STRUCTURED : FDLP_AC_STRUCTURED_MFMA;
-  } else {
-    return fail(FDLP_E_INVALID, "fdlp_set_autocorr_path: unknown path");
+    return (path == FDLP_AC_STRUCTURED && p->vs_avail) ? FDLP_AC_STRUCTURED : FDLP_AC_STRUCTURED_MFMA;
   }
+  return fail(FDLP_E_INVALID, std::string(who) + ": unknown path");
+}
+
+int fdlp_set_autocorr_path(fdlp_plan* p, int32_t path) {
+  if (!p) return fail(FDLP_E_INVALID, "fdlp_set_autocorr_path: null plan");
+  const int r = resolve_autocorr_path(p, path, "fdlp_set_autocorr_path");
+  if (r < 0) return r;
+  p->ac_path = r;
+  return FDLP_OK;
+}
+
+int fdlp_plan_autocorr_dispatch(const fdlp_plan* p, int32_t path, int32_t out[10]) {
+  if (!p || !out) return fail(FDLP_E_INVALID, "fdlp_plan_autocorr_dispatch: need a plan and out[10]");
+  const int r = resolve_autocorr_path(p, path, "fdlp_plan_autocorr_dispatch");
+  if (r < 0) return r;
+  const SkirtTables& T = p->sk;
+  fdlp::autocorr_dispatch_info(r, p->N, p->nlags, p->B, T.fl_C, T.fl_H, p->sk_avail ? T.reg.data() : nullptr,
+                               p->sk_avail && T.wrap_any ? T.wrap_kw.data() : nullptr, out);
   return FDLP_OK;
 }
 

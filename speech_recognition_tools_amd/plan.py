@@ -176,6 +176,24 @@ class FdlpPlan:
     def set_autocorr_path(self, path: str = "auto"):
         check(lib.fdlp_set_autocorr_path(self._h, self.AUTOCORR_PATHS[path]))
 
+    def autocorr_dispatch(self) -> dict:
+        """What the autocorrelation stage launches for 'auto' and for each explicit path that the plan has
+        (fdlp_plan_autocorr_dispatch; also on a host-only plan), {request: dict}: ``path`` the path launched,
+        ``tiles`` NT of the MFMA kernels and, on 'structured' (0 / False elsewhere), ``lanes_lags`` A and
+        ``chain_slots`` C of ac_vsweep_kernel<A, C>, the ``chains`` the flat tops need, the flat sweep's
+        position ``parts``, ``fast22_skirt`` / ``fast22_flat`` (plain runs in the 2x2 form), ``wrap_shared``
+        (ac_wrap_kernel runs) and ``fast_bands`` (bands in ac_band_kernel's compact staging)."""
+        names = {1: "direct", 2: "structured", 3: "structured_mfma"}
+        res = {}
+        for req, code in self.AUTOCORR_PATHS.items():
+            v = (_lib.c_i32 * 10)()
+            if lib.fdlp_plan_autocorr_dispatch(self._h, code, v) != 0:
+                continue  # no structured paths for this filterbank
+            path, nt, a, c, slots, parts, fs, ff, wrap, fast = (int(x) for x in v)
+            res[req] = dict(path=names[path], tiles=nt, lanes_lags=a, chains=c, chain_slots=slots, parts=parts,
+                            fast22_skirt=bool(fs), fast22_flat=bool(ff), wrap_shared=bool(wrap), fast_bands=fast)
+        return res
+
     LPC_PATHS = {"auto": 0, "lds": 1, "lattice8": 2}
 
     def set_lpc_path(self, path: str = "auto"):

@@ -12,6 +12,18 @@ CFGS = [FeatureConfig.wsj(),
                       coeff_range="0,40")]
 
 
+def _row(fb, nf, fd, order):
+    return FeatureConfig(fbank_type=fb, nfilters=nf, fduration=fd, order=order, coeff_num=10, coeff_range="0,10")
+
+
+# rows 12, 13, 14 and 20 of tests/test_autocorr_dispatch.py: 8 chains, 7 chains in 8 slots, 8 chains in one
+# position part, flat tops of width 0 and 1
+ROW_CFGS = {"c8": _row("cochlear,8,1,1,2.5,1", 20, 0.5, 150), "c7of8": _row("cochlear,8,1,1,2.5,1", 16, 0.5, 150),
+            "c8h1": _row("cochlear,8,1,1,2.5,1", 20, 0.1, 150), "empty": _row("cochlear,0.0001,1,1,2.5,1", 10, 0.5, 20)}
+EMU_CFGS = CFGS + list(ROW_CFGS.values())
+EMU_IDS = ["wsj", "wide"] + list(ROW_CFGS)
+
+
 @pytest.mark.parametrize("cfg", CFGS, ids=["wsj", "wide"])
 def test_flat_event_table(cfg):
     p = FdlpPlan(cfg, device=-1, max_frames=4)
@@ -78,7 +90,12 @@ def _emulate(D, m1, m2, C, H, ev, nl):
     return flat
 
 
-@pytest.mark.parametrize("cfg", CFGS, ids=["wsj", "wide"])
+def test_row_cfgs_have_their_chains():
+    got = {k: FdlpPlan(cfg, device=-1, max_frames=4).flat_events()[:2] for k, cfg in ROW_CFGS.items()}
+    assert got == {"c8": (8, 2), "c7of8": (7, 2), "c8h1": (8, 1), "empty": (1, 2)}
+
+
+@pytest.mark.parametrize("cfg", EMU_CFGS, ids=EMU_IDS)
 def test_flat_chain_emulation_matches_direct_sums(cfg):
     p = FdlpPlan(cfg, device=-1, max_frames=4)
     m1, m2 = p.regions()

@@ -25,11 +25,12 @@ def test_library_exports_every_header_symbol():
     from speech_recognition_tools_amd import _lib
     syms = header_symbols()
     assert len(syms) >= 25
-    assert {"fdlp_dct_rows", "fdlp_lpc_rows", "fdlp_cepstrum_rows", "fdlp_ola_rows", "fdlp_ola_info"} <= set(syms)
+    assert {"fdlp_dct_rows", "fdlp_lpc_rows", "fdlp_cepstrum_rows", "fdlp_ola_rows", "fdlp_ola_info",
+            "fdlp_plan_autocorr_dispatch"} <= set(syms)
     for name in syms:
         assert hasattr(_lib.lib, name), name
     assert set(syms) == set(_lib.SIGNATURES), set(syms) ^ set(_lib.SIGNATURES)
-    assert _lib.lib.fdlp_abi_version() == 11
+    assert _lib.lib.fdlp_abi_version() == 12
 
 
 @pytest.mark.parametrize("seed", [0, 1, 7, 1234, 2 ** 40 + 5, 2 ** 64 + 3])

@@ -208,7 +208,7 @@ def test_new_entry_points_are_declared_and_exported():
     for n in names:
         assert n in declared and n in _lib.SIGNATURES and hasattr(_lib.lib, n), n
     assert sorted(n for n in _lib.SIGNATURES if "xform" in n) == sorted(names)
-    assert "#define FDLP_ABI_VERSION 11" in src and _lib.lib.fdlp_abi_version() == 11
+    assert "#define FDLP_ABI_VERSION 12" in src and _lib.lib.fdlp_abi_version() == 12
     # a host-only plan refuses to compute, and null arguments are refused
     import ctypes
     from speech_recognition_tools_amd._lib import FdlpError, FdlpPostBatchC, check

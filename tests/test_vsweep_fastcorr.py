@@ -8,7 +8,10 @@ differences of neighbouring window elements and sums of neighbouring positions, 
   lsb          noise of 1 LSB amplitude (values -1, 0, 1): scale
 
 Shapes: the three lag widths of test_vsweep_block_order.py (A = 4, 8, 10 lags per lane) at F = 1 (a last group of
-four with three invalid rows) and F = 5 (two groups), max_frames = 64.
+four with three invalid rows) and F = 5 (two groups), max_frames = 64.  The skirt sweeps <A, 0> take the 2x2 form
+at all three widths; the flat sweep takes it at a4 (<4, 4>) and a10 (<10, 5>) only: the a8 row needs one chain and
+runs <8, 4>, which vs_fast22 leaves in the direct form.  The 2x2 form in the flat sweep at A = 8 (<8, 5>, <8, 6>,
+<8, 8>) is held by rows 5, 8 and 11 of test_autocorr_dispatch.py, on the same inputs.
 
 Bar: max over lags of |dr| / r[0] <= 1e-12, the project's; the VALU and the MFMA sweeps agree to 2e-12.  The bar
 presumes that the oracle's own r is far inside it for these inputs: test_oracle_is_inside_the_bar holds it, at
