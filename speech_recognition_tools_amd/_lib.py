@@ -127,6 +127,17 @@ class FdlpMmodConfigC(ctypes.Structure):
                 ("n_sub_layers", c_i32), ("hidden_sub", c_i32), ("n_trunk_layers", c_i32), ("n_classes", c_i32)]
 
 
+FDLP_VENC_MAX_CONV = 8
+FDLP_VENC_RNN, FDLP_VENC_CNN = 0, 1
+
+
+class FdlpVencConfigC(ctypes.Structure):
+    _fields_ = [("post", FdlpPostConfigC), ("arch", c_i32), ("in_dim", c_i32), ("n_enc_layers", c_i32),
+                ("enc_hidden", c_i32), ("n_conv", c_i32), ("channels", c_i32 * (FDLP_VENC_MAX_CONV + 1)),
+                ("kh", c_i32), ("kw", c_i32), ("feat_h", c_i32), ("latent_dim", c_i32), ("n_cls_layers", c_i32),
+                ("cls_hidden", c_i32), ("n_classes", c_i32)]
+
+
 class FdlpPostBatchC(ctypes.Structure):
     _fields_ = [
         ("n_utt", c_i32), ("norm_mul", c_i32), ("in_dev", c_p), ("n_rows", c_i64), ("row_off", P_i64),
@@ -263,6 +274,14 @@ SIGNATURES = {
     "fdlp_mmod_compute": (c_i32, [c_p, ctypes.POINTER(FdlpPostBatchC), c_i32, c_i32, c_p, ctypes.c_float, c_p]),
     "fdlp_mmod_set_profiling": (c_i32, [c_p, c_i32]),
     "fdlp_mmod_times": (c_i32, [c_p, P_dbl]),
+    "fdlp_venc_create": (c_i32, [ctypes.POINTER(FdlpVencConfigC), ctypes.POINTER(c_p), c_i64, c_i32,
+                                      ctypes.POINTER(c_p)]),
+    "fdlp_venc_plan_destroy": (c_i32, [c_p]),
+    "fdlp_venc_plan_info": (c_i32, [c_p, P_i32, P_i32, P_i32, P_i64, P_i32, P_i32]),
+    "fdlp_venc_plan_groups": (c_i32, [c_p, P_i32, c_i32, P_i32, P_i32, P_i32]),
+    "fdlp_venc_compute": (c_i32, [c_p, ctypes.POINTER(FdlpPostBatchC), c_i32, c_i32, c_p, ctypes.c_float, c_p]),
+    "fdlp_venc_set_profiling": (c_i32, [c_p, c_i32]),
+    "fdlp_venc_times": (c_i32, [c_p, P_dbl]),
     "fdlp_cmvn_norm": (c_i32, [P_dbl, c_i32, c_i32, c_i32, c_i32, P_i32, c_i32, ctypes.POINTER(ctypes.c_float)]),
     "fdlp_noise_params_f64": (c_i32, [P_dbl, c_i64, P_i16, c_i64, c_dbl, c_dbl, P_i64, P_dbl]),
     "fdlp_mat_reader_open": (c_i32, [ctypes.c_char_p, ctypes.POINTER(c_p)]),

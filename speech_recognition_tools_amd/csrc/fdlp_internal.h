@@ -343,6 +343,30 @@ hipError_t launch_gru_scan_streams(const GruStreams& st, int n_streams, int ldo,
                                    int64_t rows, int H, hipStream_t s);
 hipError_t checks_nnet(unsigned int* v, bool reset);
 
+// The VAE-encoded models (fdlp_vaeenc.hip).  conv2d_same_kernel: one same-padded Conv2d over rows [t][c F + f]; GEMM
+// rows are the positions p = t F + f of ONE utterance, a ConvTile the kDenseTM positions from p0, and the chain of
+// every output is dense_kernel's at K = Ci kh kw (k the flat index of W[co] in (ci, dh, dw)).  koff: the device copy
+// of conv_koff_table's ceil(K / kDenseKC) kDenseKC offsets into the staged input patch.
+struct ConvTile {
+  int64_t row0;        // batch row of the utterance's frame 0 (input and output rows coincide)
+  int32_t T, p0;       // utterance frames; first position of the tile, a multiple of kDenseTM below T F
+};
+struct ConvConsts {
+  int F, Ci, Co, kh, kw;
+  int K, KP, NFR, patch_floats;  // Ci kh kw, K rounded up to kDenseKC, frames and floats of the staged patch
+};
+int conv_patch_frames(int F, int kw);
+size_t conv_lds_bytes(int F, int Ci, int Co, int kh, int kw);  // LDS bytes of a workgroup
+void conv_koff_table(int F, int Ci, int kh, int kw, int32_t* koff);
+hipError_t launch_conv2d_same(const float* in, const float* W, const float* bias, float* out, const ConvTile* tiles,
+                              int ntiles, const int32_t* koff, int64_t rows, int F, int Ci, int Co, int kh, int kw,
+                              int relu, hipStream_t s);
+// utt_norm_kernel: out = (z - mean_t z) / sqrt(var_t), unbiased, per utterance (a GruSlot; len 0 = empty) and column
+// of z [rows, D]; in == out is allowed
+hipError_t launch_utt_norm(const float* in, float* out, const GruSlot* slots, int n_slots, int64_t rows, int D,
+                           hipStream_t s);
+hipError_t checks_vaeenc(unsigned int* v, bool reset);  // summed into checks_nnet
+
 // One utterance of a reverb batch (fdlp_reverb): samples at pcm[off, off+T), y at [yoff, yoff+T+R-1).
 struct RevUtt {
   int64_t off, T, yoff, noff;  // noff < 0: no noise mixing

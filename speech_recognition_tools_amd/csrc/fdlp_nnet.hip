@@ -520,6 +520,15 @@ hipError_t launch_gru_scan(const float* G, const float* Whh, const float* bhh, f
   return launch_gru_scan_streams(st, 1, H, slots, n_groups, rows, H, s);
 }
 
-hipError_t checks_nnet(unsigned int* v, bool reset) { return fdlp_checks_local(v, reset); }
+// this translation unit's counters and fdlp_vaeenc.hip's (the kernels of the same model family)
+hipError_t checks_nnet(unsigned int* v, bool reset) {
+  unsigned int w[2] = {0u, 0u};
+  hipError_t e = fdlp_checks_local(v, reset);
+  if (e != hipSuccess) return e;
+  if ((e = checks_vaeenc(w, reset)) != hipSuccess) return e;
+  v[0] += w[0];
+  v[1] = v[1] > w[1] ? v[1] : w[1];
+  return hipSuccess;
+}
 
 }  // namespace fdlp

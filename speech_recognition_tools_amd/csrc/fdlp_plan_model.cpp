@@ -19,6 +19,17 @@ struct StageWords {
 };
 static const StageWords kRnnWords = {"fdlp_rnn_plan_create", "fdlp_rnn_compute", "model", "stage"};
 static const StageWords kNnetWords = {"fdlp_nnet_plan_create", "fdlp_nnet_compute", "network", "layer"};
+static const StageWords kVencWords = {"fdlp_venc_create", "fdlp_venc_compute", "model", "stage"};
+
+// Stage kinds beside the public FDLP_RNN_*: only the venc front (at the bottom) makes them, with a ConvGeom.
+//   kStageConv  a same-padded Conv2d over rows [t][c F + f] (conv2d_same_kernel), {w [Co, Ci, kh, kw], -, b, -};
+//               dims[s] = Ci F, dims[s + 1] = Co F; its ReLU is applied when the next stage loads the output
+//   kStageNorm  the per-utterance normaliser (utt_norm_kernel), no parameters, dims[s + 1] = dims[s]
+// A plan whose stage 0 is a conv runs the plain chain (post_kernel) in front of it instead of a fused transform.
+enum { kStageConv = 3, kStageNorm = 4 };
+struct ConvGeom {
+  int F, kh, kw;
+};
 
 // Utterances sorted by length, descending and stable, cut into groups of kGruGU: order[i] is the utterance in
 // slot i % kGruGU of group i / kGruGU
@@ -86,14 +97,15 @@ struct LaunchMarks {
     }
     marks.clear();
   }
-  // ms[0] the projections and linear stages, ms[1] the scans since the last call; waits for them
-  int times(double* ms) {
-    ms[0] = ms[1] = 0.0;
+  // ms[0] the projections and linear stages, ms[1] the scans, ms[2] (n = 3: the venc front) the convolutions since
+  // the last call; waits for them
+  int times(double* ms, int n = 2) {
+    for (int i = 0; i < n; ++i) ms[i] = 0.0;
     for (auto& m : marks) {
       float t = 0.f;
       HIP_TRY(hipEventSynchronize(m.second.second));
       HIP_TRY(hipEventElapsedTime(&t, m.second.first, m.second.second));
-      ms[m.first] += t;
+      ms[std::min(m.first, n - 1)] += t;
     }
     drop();
     return FDLP_OK;
@@ -108,13 +120,21 @@ struct fdlp_rnn_plan {
   int64_t max_rows = 0;
   int max_utts = 0;             // 0 behind the nnet front (as gt.max_groups): no scans, no group table, any n_utt
   int max_h = 0;                // widest GRU, 0 without one
-  int widest = 0;               // widest of dims[1 .. n_stages - 1], 0 with one stage
+  int widest = 0;               // widest of dims[1 .. n_stages - 1] (with a conv stage 0, which reads a workspace,
+                                // of dims[0 .. n_stages - 1]), 0 with one stage
   float* d_m0 = nullptr;        // [N_0, dims[0] + 1], N_0 = dims[1] or 3 dims[1]
   std::vector<float*> d_p;      // 4 per stage: w_ih | w, w_hh, b_ih | b, b_hh (stage 0: w_hh and b_hh only)
   float* d_g = nullptr;
   float* d_ws[2] = {nullptr, nullptr};
   GroupTable gt;
   LaunchMarks lm;
+  // conv stages (the venc front with a CNN encoder): the image height and the kernel, the plain chain in front of
+  // a conv stage 0, a koff table per conv stage, the tile table of a batch (one for all layers: it depends on F alone)
+  ConvGeom cg{0, 0, 0};
+  std::unique_ptr<fdlp_post_plan> c0;
+  std::vector<int32_t*> d_koff;
+  Staging<fdlp::ConvTile> ctiles;
+  size_t conv_lds = 0;
   DeviceResources res;
 };
 
@@ -132,8 +152,10 @@ static int zeroed_workspace(DeviceResources& res, float** ws, size_t n, const ch
 }
 
 // max_utts = 0 (the nnet front; legal without a GRU only): no scans, so no group table, staging or event
+// cg: the geometry of the conv stages; without it only the public kinds are known
 static int stage_plan_create(const fdlp_rnn_config* cfg, const float* const* params, int64_t max_rows,
-                             int32_t max_utts, const StageWords& w, fdlp_rnn_plan** out) {
+                             int32_t max_utts, const StageWords& w, fdlp_rnn_plan** out,
+                             const ConvGeom* cg = nullptr) {
   *out = nullptr;
   const int ns = cfg->n_stages;
   if (ns < 1 || ns > FDLP_RNN_MAX_STAGES)
@@ -142,7 +164,8 @@ static int stage_plan_create(const fdlp_rnn_config* cfg, const float* const* par
   std::string shape;
   for (int s = 0; s <= ns; ++s) shape += (s ? " -> " : "") + std::to_string(cfg->dims[s]);
   for (int s = 0; s < ns; ++s)
-    if (cfg->kind[s] != FDLP_RNN_GRU && cfg->kind[s] != FDLP_RNN_LINEAR && cfg->kind[s] != FDLP_RNN_LINEAR_RELU)
+    if (cfg->kind[s] != FDLP_RNN_GRU && cfg->kind[s] != FDLP_RNN_LINEAR && cfg->kind[s] != FDLP_RNN_LINEAR_RELU &&
+        !(cg && (cfg->kind[s] == kStageConv || (cfg->kind[s] == kStageNorm && s > 0))))
       return fail(FDLP_E_INVALID, "stage " + std::to_string(s) + " has the unknown kind " +
                                       std::to_string(cfg->kind[s]) + " (0 GRU, 1 linear, 2 linear with ReLU)");
   for (int s = 0; s <= ns; ++s)
@@ -160,10 +183,39 @@ static int stage_plan_create(const fdlp_rnn_config* cfg, const float* const* par
     return fail(FDLP_E_INVALID, "a GRU of " + std::to_string(max_h) + " hidden units needs " +
                                     std::to_string(fdlp::gru_lds_bytes(max_h)) + " bytes of the 163840-byte LDS; the "
                                     "widest that fits has " + std::to_string(fdlp::gru_max_hidden()));
+  size_t conv_lds = 0;
+  for (int s = 0; s < ns; ++s) {
+    if (cfg->kind[s] == kStageNorm && cfg->dims[s + 1] != cfg->dims[s])
+      return fail(FDLP_E_INVALID, "stage " + std::to_string(s) + " normalises " + std::to_string(cfg->dims[s]) +
+                                      " columns into " + std::to_string(cfg->dims[s + 1]));
+    if (cfg->kind[s] != kStageConv) continue;
+    const int F = cg->F, Ci = cfg->dims[s] / std::max(F, 1), Co = cfg->dims[s + 1] / std::max(F, 1);
+    if (F < 1 || cg->kh < 1 || cg->kw < 1 || cg->kh % 2 == 0 || cg->kw % 2 == 0)
+      return fail(FDLP_E_INVALID, "a same-padded convolution needs an odd kernel and a height >= 1, got kernel (" +
+                                      std::to_string(cg->kh) + ", " + std::to_string(cg->kw) + ") at height " +
+                                      std::to_string(F));
+    if (Ci * F != cfg->dims[s] || Co * F != cfg->dims[s + 1])
+      return fail(FDLP_E_INVALID, "stage " + std::to_string(s) + " is a convolution at height " + std::to_string(F) +
+                                      " from " + std::to_string(cfg->dims[s]) + " to " +
+                                      std::to_string(cfg->dims[s + 1]) + " columns, which are not whole channels");
+    const int64_t K = (int64_t)Ci * cg->kh * cg->kw;
+    const double need = K > (1 << 24) ? 4.0 * (double)K : (double)fdlp::conv_lds_bytes(F, Ci, Co, cg->kh, cg->kw);
+    if (need > 163840.0)
+      return fail(FDLP_E_INVALID, "the convolution of stage " + std::to_string(s) + ", " + std::to_string(Ci) +
+                                      " -> " + std::to_string(Co) + " channels, kernel (" + std::to_string(cg->kh) +
+                                      ", " + std::to_string(cg->kw) + ") at height " + std::to_string(F) +
+                                      ", needs " + std::to_string((long long)need) +
+                                      " bytes of the 163840-byte LDS (the staged input patch holds " +
+                                      std::to_string(fdlp::conv_patch_frames(F, cg->kw)) + " frames of " +
+                                      std::to_string((int64_t)Ci * (F + cg->kh - 1)) + " floats)");
+    conv_lds = std::max(conv_lds, (size_t)need);
+  }
+  const bool conv0 = cfg->kind[0] == kStageConv;
   const bool dev = cfg->post.device >= 0;
   if (dev && !params) return fail(FDLP_E_INVALID, std::string(w.create) + ": null parameters");
   for (int s = 0; dev && s < ns; ++s) {
     const bool gru = cfg->kind[s] == FDLP_RNN_GRU;
+    if (cfg->kind[s] == kStageNorm) continue;
     if (!params[4 * s] || !params[4 * s + 2] || (gru && (!params[4 * s + 1] || !params[4 * s + 3])))
       return fail(FDLP_E_INVALID, std::string(w.create) + ": null parameters of " + w.stage + " " + std::to_string(s));
   }
@@ -178,18 +230,27 @@ static int stage_plan_create(const fdlp_rnn_config* cfg, const float* const* par
   p->max_utts = max_utts;
   p->gt.max_groups = (max_utts + fdlp::kGruGU - 1) / fdlp::kGruGU;
   p->max_h = max_h;
-  for (int s = 1; s < ns; ++s) p->widest = std::max(p->widest, cfg->dims[s]);
+  for (int s = conv0 ? 0 : 1; s < ns; ++s) p->widest = std::max(p->widest, cfg->dims[s]);  // a conv stage 0 reads a workspace
   p->d_p.assign((size_t)ns * 4, nullptr);
+  p->d_koff.assign((size_t)ns, nullptr);
+  if (cg) p->cg = *cg;
+  p->conv_lds = conv_lds;
   int rc;
   const int N0 = cfg->kind[0] == FDLP_RNN_GRU ? 3 * cfg->dims[1] : cfg->dims[1];
-  fdlp_xform_config xc{};
-  xc.post = cfg->post;
-  xc.out_dim = N0;
-  xc.affine = 1;
-  fdlp_xform_plan* l0 = nullptr;
-  if ((rc = fdlp_xform_plan_create(&xc, &l0)) != FDLP_OK) return rc;
-  p->l0.reset(l0);
-  const int K0 = p->l0->post->Dout;
+  if (conv0) {
+    fdlp_post_plan* c0 = nullptr;
+    if ((rc = fdlp_post_plan_create(&cfg->post, &c0)) != FDLP_OK) return rc;
+    p->c0.reset(c0);
+  } else {
+    fdlp_xform_config xc{};
+    xc.post = cfg->post;
+    xc.out_dim = N0;
+    xc.affine = 1;
+    fdlp_xform_plan* l0 = nullptr;
+    if ((rc = fdlp_xform_plan_create(&xc, &l0)) != FDLP_OK) return rc;
+    p->l0.reset(l0);
+  }
+  const int K0 = conv0 ? p->c0->Dout : p->l0->post->Dout;
   if (K0 != cfg->dims[0])
     return fail(FDLP_E_INVALID, std::string("the ") + w.model + "'s input dimension dims[0] = " +
                                     std::to_string(cfg->dims[0]) + " differs from the " + std::to_string(K0) +
@@ -201,7 +262,7 @@ static int stage_plan_create(const fdlp_rnn_config* cfg, const float* const* par
   DeviceGuard dg(p->device);
   if (dg.status() != hipSuccess) return fail(FDLP_E_HIP, "hipSetDevice failed");
   DeviceResources& res = p->res;
-  {
+  if (!conv0) {
     // stage 0's input side as transform-feats' affine matrix: [W | b]
     std::vector<float> m0((size_t)N0 * (K0 + 1));
     for (int n = 0; n < N0; ++n) {
@@ -213,12 +274,25 @@ static int stage_plan_create(const fdlp_rnn_config* cfg, const float* const* par
   for (int s = 0; s < ns; ++s) {
     const size_t K = (size_t)cfg->dims[s], N = (size_t)cfg->dims[s + 1];
     const bool gru = cfg->kind[s] == FDLP_RNN_GRU;
+    if (cfg->kind[s] == kStageNorm) continue;
+    if (cfg->kind[s] == kStageConv) {
+      // w [Co, Ci kh kw], b [Co], and the offsets of the k into the staged patch
+      const size_t F = (size_t)cg->F, Ci = K / F, Co = N / F, Kc = Ci * cg->kh * cg->kw;
+      if ((rc = upload(res, &p->d_p[4 * (size_t)s], params[4 * s], Co * Kc)) != FDLP_OK ||
+          (rc = upload(res, &p->d_p[4 * (size_t)s + 2], params[4 * s + 2], Co)) != FDLP_OK)
+        return rc;
+      std::vector<int32_t> koff((Kc + fdlp::kDenseKC - 1) / fdlp::kDenseKC * fdlp::kDenseKC);
+      fdlp::conv_koff_table((int)F, (int)Ci, cg->kh, cg->kw, koff.data());
+      if ((rc = upload(res, &p->d_koff[(size_t)s], koff.data(), koff.size())) != FDLP_OK) return rc;
+      continue;
+    }
     // w_ih | w, w_hh, b_ih | b, b_hh; stage 0's input side is d_m0
     const size_t count[4] = {s > 0 ? (gru ? 3 * N : N) * K : 0, gru ? 3 * N * N : 0, s > 0 ? (gru ? 3 * N : N) : 0,
                              gru ? 3 * N : 0};
     for (int i : {0, 2, 1, 3})  // the input side first
       if (count[i] && (rc = upload(res, &p->d_p[4 * (size_t)s + i], params[4 * s + i], count[i])) != FDLP_OK) return rc;
   }
+  if (conv_lds && p->ctiles.event(res) != hipSuccess) return fail(FDLP_E_NOMEM, "stage plan: event creation failed");
   if ((rc = zeroed_workspace(res, &p->d_g, (size_t)max_rows * 3 * p->max_h, "the projection buffer", max_rows)) != FDLP_OK)
     return rc;
   for (float*& ws : p->d_ws)
@@ -356,7 +430,7 @@ static int stage_compute(fdlp_rnn_plan* p, const fdlp_post_batch* b, int32_t tap
   if (p->device < 0) return fail(FDLP_E_INVALID, std::string(words.compute) + ": host-only plan");
   {
     const int rc = stage_check_call(words, p->n_stages, tap, mode, prior_dev, b, p->max_utts, p->max_rows,
-                                    p->max_h > 0);
+                                    p->max_h > 0 || p->conv_lds > 0);
     if (rc != FDLP_OK) return rc;
   }
   const int last = p->n_stages - 1 - tap;  // the tapped stage
@@ -367,14 +441,18 @@ static int stage_compute(fdlp_rnn_plan* p, const fdlp_post_batch* b, int32_t tap
   DeviceGuard dg(p->device);
   HIP_TRY(dg.status());
   LaunchMarks& lm = p->lm;
-  // stage 0's input side in the chain's launch; its batch checks are the chain's
+  auto kind = [&](int st) { return p->kind[(size_t)st]; };
+  const bool conv0 = kind(0) == kStageConv;
+  // stage 0's input side in the chain's launch (a conv stage 0: the plain chain into the workspace it reads); its
+  // batch checks are the chain's
   fdlp_post_batch b0 = *b;
-  b0.out_dev = gru(0) ? p->d_g : dst(0);
+  b0.out_dev = conv0 ? p->d_ws[1] : gru(0) ? p->d_g : dst(0);
   fdlp::XformConsts xc{};
   xc.N = gru(0) ? 3 * p->dims[1] : p->dims[1]; xc.C = p->dims[0] + 1; xc.affine = 1; xc.n_mat = 1;
   HIP_TRY(lm.begin(s));
   {
-    const int rc = post_compute(p->l0->post.get(), &b0, stream, &xc, p->d_m0, nullptr);
+    const int rc = conv0 ? post_compute(p->c0.get(), &b0, stream, nullptr, nullptr, nullptr)
+                         : post_compute(p->l0->post.get(), &b0, stream, &xc, p->d_m0, nullptr);
     if (rc != FDLP_OK) return rc;
   }
   HIP_TRY(lm.end(0, s));
@@ -384,6 +462,43 @@ static int stage_compute(fdlp_rnn_plan* p, const fdlp_post_batch* b, int32_t tap
     const int rc = p->gt.stage(b, s, &ng);
     if (rc != FDLP_OK) return rc;
   }
+  // the conv tiles of the batch, once for all conv stages: kDenseTM positions p = t F + f of one utterance each
+  size_t nct = 0;
+  if (p->conv_lds) {
+    const int F = p->cg.F;
+    for (int u = 0; u < b->n_utt; ++u) {
+      if (b->utt_len[u] > INT32_MAX / F)
+        return fail(FDLP_E_CAPACITY, "utterance " + std::to_string(u) + " has " + std::to_string(b->utt_len[u]) +
+                                         " frames of height " + std::to_string(F) + ": more than 2^31 - 1 positions");
+      nct += (size_t)((b->utt_len[u] * F + fdlp::kDenseTM - 1) / fdlp::kDenseTM);
+    }
+    if (nct > (size_t)INT32_MAX) return fail(FDLP_E_CAPACITY, "too many convolution tiles in one batch");
+    int rc;
+    if ((rc = p->ctiles.wait()) != FDLP_OK) return rc;
+    if ((rc = p->ctiles.reserve(p->res, nct, "stage plan: convolution tile table allocation failed")) != FDLP_OK) return rc;
+    size_t k = 0;
+    for (int u = 0; u < b->n_utt; ++u)
+      for (int64_t p0 = 0; p0 < b->utt_len[u] * F; p0 += fdlp::kDenseTM) {
+        fdlp::ConvTile& tl = p->ctiles.host[k++];
+        tl.row0 = b->row_off[u];
+        tl.T = (int32_t)b->utt_len[u];
+        tl.p0 = (int32_t)p0;
+      }
+    if ((rc = p->ctiles.publish(nct, s)) != FDLP_OK) return rc;
+  }
+  auto conv = [&](int st, const float* in, int relu) -> int {
+    const int F = p->cg.F;
+    HIP_TRY(lm.begin(s));
+    HIP_TRY(fdlp::launch_conv2d_same(in, p->d_p[4 * (size_t)st], p->d_p[4 * (size_t)st + 2], dst(st), p->ctiles.dev,
+                                     (int)nct, p->d_koff[(size_t)st], b->n_rows, F, p->dims[(size_t)st] / F,
+                                     p->dims[(size_t)st + 1] / F, p->cg.kh, p->cg.kw, relu, s));
+    HIP_TRY(lm.end(2, s));
+    return FDLP_OK;
+  };
+  if (conv0) {
+    const int rc = conv(0, p->d_ws[1], 0);
+    if (rc != FDLP_OK) return rc;
+  }
   if (gru(0)) {
     const float* const* w = &p->d_p[0];
     HIP_TRY(lm.begin(s));
@@ -391,7 +506,19 @@ static int stage_compute(fdlp_rnn_plan* p, const fdlp_post_batch* b, int32_t tap
     HIP_TRY(lm.end(1, s));
   }
   for (int st = 1; st <= last; ++st) {
-    const int relu = p->kind[(size_t)st - 1] == FDLP_RNN_LINEAR_RELU;
+    const int relu = kind(st - 1) == FDLP_RNN_LINEAR_RELU || kind(st - 1) == kStageConv;
+    if (kind(st) == kStageConv) {
+      const int rc = conv(st, p->d_ws[(st - 1) & 1], relu);
+      if (rc != FDLP_OK) return rc;
+      continue;
+    }
+    if (kind(st) == kStageNorm) {
+      HIP_TRY(lm.begin(s));
+      HIP_TRY(fdlp::launch_utt_norm(p->d_ws[(st - 1) & 1], dst(st), p->gt.slots.dev, ng * fdlp::kGruGU, b->n_rows,
+                                    p->dims[(size_t)st], s));
+      HIP_TRY(lm.end(0, s));
+      continue;
+    }
     const int rc = stage_launch(lm, gru(st), p->d_ws[(st - 1) & 1], relu, &p->d_p[4 * (size_t)st], p->d_g, dst(st),
                                 p->gt.slots.dev, ng, b->n_rows, p->dims[(size_t)st], p->dims[(size_t)st + 1], s);
     if (rc != FDLP_OK) return rc;
@@ -461,6 +588,109 @@ int fdlp_nnet_compute(fdlp_nnet_plan* p, const fdlp_post_batch* b, int32_t tap, 
                       float prior_weight, void* stream) {
   if (!p || !b) return fail(FDLP_E_INVALID, "fdlp_nnet_compute: null argument");
   return stage_compute(stage_plan(p), b, tap, mode, prior_dev, prior_weight, stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// VAE-encoded plan (compute_vae_encoded_likelihood.py): the stage plan with the stages
+//   encoder (GRU x n_enc_layers | conv x n_conv), means (linear), norm, GRU x n_cls_layers, regression (linear).
+// fdlp_venc_plan is that plan under the name include/fdlp.h gives this front.
+// ---------------------------------------------------------------------------------------------
+static fdlp_rnn_plan* stage_plan(fdlp_venc_plan* p) { return reinterpret_cast<fdlp_rnn_plan*>(p); }
+static const fdlp_rnn_plan* stage_plan(const fdlp_venc_plan* p) { return reinterpret_cast<const fdlp_rnn_plan*>(p); }
+
+int fdlp_venc_create(const fdlp_venc_config* cfg, const float* const* params, int64_t max_rows, int32_t max_utts,
+                          fdlp_venc_plan** out) {
+  if (!cfg || !out) return fail(FDLP_E_INVALID, "fdlp_venc_create: null argument");
+  *out = nullptr;
+  if (max_utts < 1) return fail(FDLP_E_INVALID, "max_utts must be >= 1, got " + std::to_string(max_utts));
+  const bool cnn = cfg->arch == FDLP_VENC_CNN;
+  if (!cnn && cfg->arch != FDLP_VENC_RNN)
+    return fail(FDLP_E_INVALID, "unknown encoder arch " + std::to_string(cfg->arch) + " (0 RNN, 1 CNN)");
+  const int ne = cnn ? cfg->n_conv : cfg->n_enc_layers, nc = cfg->n_cls_layers;
+  if (cnn && (ne < 1 || ne > FDLP_VENC_MAX_CONV))
+    return fail(FDLP_E_INVALID, "the CNN encoder needs 1 .. " + std::to_string(FDLP_VENC_MAX_CONV) +
+                                    " convolutions, got n_conv = " + std::to_string(ne));
+  if (ne < 1 || nc < 1 || ne + nc + 3 > FDLP_RNN_MAX_STAGES)
+    return fail(FDLP_E_INVALID, "the model needs at least one encoder and one classifier layer and at most " +
+                                    std::to_string(FDLP_RNN_MAX_STAGES) + " stages, got " + std::to_string(ne) +
+                                    " + means + norm + " + std::to_string(nc) + " + regression");
+  fdlp_rnn_config sc{};
+  sc.post = cfg->post;
+  sc.n_stages = ne + nc + 3;
+  ConvGeom cg{cfg->feat_h, cfg->kh, cfg->kw};
+  int s = 0;
+  if (cnn) {
+    if (cfg->kh < 1 || cfg->kw < 1 || cfg->kh % 2 == 0 || cfg->kw % 2 == 0)
+      return fail(FDLP_E_INVALID, "a same-padded convolution needs an odd kernel, got (" + std::to_string(cfg->kh) +
+                                      ", " + std::to_string(cfg->kw) + ")");
+    if (cfg->channels[0] != 1)
+      return fail(FDLP_E_INVALID, "the first convolution reads the one-channel feature image, got channels[0] = " +
+                                      std::to_string(cfg->channels[0]));
+    if (cfg->feat_h < 1) return fail(FDLP_E_INVALID, "feat_h must be >= 1, got " + std::to_string(cfg->feat_h));
+    for (int l = 0; l <= ne; ++l) {
+      if (cfg->channels[l] < 1 || (int64_t)cfg->channels[l] * cfg->feat_h > INT32_MAX)
+        return fail(FDLP_E_INVALID, "channels[" + std::to_string(l) + "] = " + std::to_string(cfg->channels[l]) +
+                                        " at height " + std::to_string(cfg->feat_h) + " is outside 1 .. 2^31 - 1 columns");
+      sc.dims[l] = cfg->channels[l] * cfg->feat_h;
+    }
+    for (; s < ne; ++s) sc.kind[s] = kStageConv;
+  } else {
+    sc.dims[0] = cfg->in_dim;
+    for (; s < ne; ++s) {
+      sc.kind[s] = FDLP_RNN_GRU;
+      sc.dims[s + 1] = cfg->enc_hidden;
+    }
+  }
+  sc.kind[s] = FDLP_RNN_LINEAR; sc.dims[++s] = cfg->latent_dim;   // means
+  sc.kind[s] = kStageNorm; sc.dims[++s] = cfg->latent_dim;
+  for (int l = 0; l < nc; ++l) {
+    sc.kind[s] = FDLP_RNN_GRU;
+    sc.dims[++s] = cfg->cls_hidden;
+  }
+  sc.kind[s] = FDLP_RNN_LINEAR; sc.dims[++s] = cfg->n_classes;    // regression
+  fdlp_rnn_plan* p = nullptr;
+  const int rc = stage_plan_create(&sc, params, max_rows, max_utts, kVencWords, &p, &cg);
+  *out = reinterpret_cast<fdlp_venc_plan*>(p);
+  return rc;
+}
+
+int fdlp_venc_plan_destroy(fdlp_venc_plan* p) { return fdlp_rnn_plan_destroy(stage_plan(p)); }
+
+int fdlp_venc_plan_info(const fdlp_venc_plan* vp, int32_t* in_dim, int32_t* n_stages, int32_t* out_dims,
+                        int64_t* workspace_bytes, int32_t* group_utts, int32_t* lds_bytes) {
+  if (!vp) return fail(FDLP_E_INVALID, "fdlp_venc_plan_info: null plan");
+  const fdlp_rnn_plan* p = stage_plan(vp);
+  stage_plan_sizes(p, in_dim, n_stages, out_dims, workspace_bytes);
+  if (group_utts) *group_utts = fdlp::kGruGU;
+  if (lds_bytes) {
+    lds_bytes[0] = p->max_h ? (int32_t)fdlp::gru_lds_bytes(p->max_h) : 0;
+    lds_bytes[1] = (int32_t)p->conv_lds;
+  }
+  return FDLP_OK;
+}
+
+int fdlp_venc_plan_groups(const fdlp_venc_plan* p, const int32_t* lengths, int32_t n_utts, int32_t* group_of,
+                          int32_t* slot_of, int32_t* n_groups) {
+  if (!p) return fail(FDLP_E_INVALID, "fdlp_venc_plan_groups: bad arguments");
+  return group_table_of("fdlp_venc_plan_groups", lengths, n_utts, group_of, slot_of, n_groups);
+}
+
+int fdlp_venc_compute(fdlp_venc_plan* p, const fdlp_post_batch* b, int32_t tap, int32_t mode, const void* prior_dev,
+                      float prior_weight, void* stream) {
+  if (!p || !b) return fail(FDLP_E_INVALID, "fdlp_venc_compute: null argument");
+  return stage_compute(stage_plan(p), b, tap, mode, prior_dev, prior_weight, stream);
+}
+
+int fdlp_venc_set_profiling(fdlp_venc_plan* p, int32_t on) {
+  if (!p) return fail(FDLP_E_INVALID, "fdlp_venc_set_profiling: null plan");
+  stage_plan(p)->lm.profile = on != 0;
+  return FDLP_OK;
+}
+
+int fdlp_venc_times(fdlp_venc_plan* p, double* ms) {
+  if (!p || !ms) return fail(FDLP_E_INVALID, "fdlp_venc_times: null argument");
+  DeviceGuard dg(stage_plan(p)->device);
+  return stage_plan(p)->lm.times(ms, 3);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -168,10 +168,11 @@ class FeedforwardCheckpoint:
 HEADER_KEYS = ("feature_dim", "num_frames", "num_layers", "hidden_dim", "num_classes")
 
 
-def open_checkpoint(path: str, keys: Sequence[str], zero_ok: Sequence[str] = (), hint: str = ""):
+def open_checkpoint(path: str, keys: Sequence[str], zero_ok: Sequence[str] = (), hint: str = "", whole: bool = False):
     """(header, model_state_dict) of a dict the reference's trainers save: header[k] = int(d[k]) for k in keys, each
     >= 1, or >= 0 for those of zero_ok.  A missing file is an OSError that names it; everything else a ValueError
-    that names the path and the key (`hint` is appended where a key is missing)."""
+    that names the path and the key (`hint` is appended where a key is missing).  whole: the dict itself as a third
+    value, for a caller whose header holds more than integers."""
     with open(path, "rb"):   # a missing or unreadable file is an OSError that names it
         pass
     try:
@@ -194,7 +195,7 @@ def open_checkpoint(path: str, keys: Sequence[str], zero_ok: Sequence[str] = (),
     sd = d["model_state_dict"]
     if not hasattr(sd, "keys"):
         raise ValueError("%s: key 'model_state_dict' is a %s, not a dict" % (path, type(sd).__name__))
-    return hdr, sd
+    return (hdr, sd, d) if whole else (hdr, sd)
 
 
 def state_array(path, sd, name, want, hdr, conv1d=False):

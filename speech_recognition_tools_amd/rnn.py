@@ -17,7 +17,9 @@ pseudo log-likelihoods latgen-faster-mapped consumes.
     `cmvn_utt,<scp>` a table of per-utterance stats, --norm-vars=true, an utterance without stats is warned about,
     counted as an error and skipped, as Kaldi does; anything else is raw.
   * --ae_type=vae samples its latent and --ae_type=vaeenc loads a path hard-coded in the reference: neither is
-    reproduced, both exit 1 with a message.  --add_softmax uses the max-subtracted form nnet.py documents.
+    reproduced, both exit 1 with a message (the deterministic form of that family, which reads the encoder's path
+    from the checkpoint, is compute-vae-encoded-likelihood, vaeenc.py).  --add_softmax uses the max-subtracted form
+    nnet.py documents.
 Out of scope: training, and the CURL and CNN models (the multi-stream model is multimod.py).
 
 The plan's compute, the runner, the file readers and the command line's body are nnet.py's (StagePlan, NnetRunner,
