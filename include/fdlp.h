@@ -681,6 +681,56 @@ int fdlp_venc_compute(fdlp_venc_plan* plan, const fdlp_post_batch* batch, int32_
 int fdlp_venc_set_profiling(fdlp_venc_plan* plan, int32_t on);
 int fdlp_venc_times(fdlp_venc_plan* plan, double* ms);
 
+/* ---- compute-lifelong-likelihood, compute-incremental-likelihood: after the logits of D model pairs ---------- */
+/* src/nnet/compute_lifelong_likelihood.py and compute_incremental_likelihood.py of the reference run D (nnetRNN,
+ * nnetVAE) pairs on one feature stream and fuse the D posterior streams with per-utterance task weights.  The forward
+ * passes are fdlp_rnn_* plans (the classifiers in mode FDLP_NNET_SOFTMAX); these four stateless calls are everything
+ * after them (kernels of fdlp_lifelong.hip).  They work on the CURRENT device, on `stream`, and return at once.
+ * post is [n_models, n_rows, n_classes] float32; row_off and utt_len are DEVICE int64 [n_utt] tables (utterance u is
+ * rows row_off[u] .. row_off[u] + utt_len[u] - 1; the caller uploads them once for the calls of a batch).  Every
+ * float64 operation is rounded as written, and every sum runs in an order fixed by the utterance's length T,
+ * n_classes = C and n_models = D alone: no result depends on the utterance's place in the batch or on the batch.
+ *
+ * fdlp_life_mmeasure (mmeasure_kernel), mmeasure_loss of the scripts, per (utterance, model) into out [n_utt, D]
+ * float64.  P [T, C] the posteriors; for d in (5, 25, 45, 65): X = P[d:], Y = P[:-d], n = max(T - d, 0), lx = log X
+ * and ly = log Y the float64 logarithms of the float32 values, dl = lx - ly:
+ *     S1_d = sum (X dl - Y dl)       sym_kld's two sums pair by pair: (X - Y)(lx - ly), with a NaN for a zero on either side
+ *     S2_d = sum X (lx - Y)          nn.KLDivLoss()(P[:-d], P[d:]) as written there: the input NOT in log space
+ *     M = (sum_d (S1_d / n + S2_d / (n C))) / 4,   d ascending from 0.0
+ * T <= 65 gives 0 / 0 = NaN and a posterior that underflowed to 0 gives NaN, as the reference does.  Order of a sum:
+ * t ascending per column; the columns of a tile of 64 ascending; the tiles ascending.  Every posterior is read once
+ * (an LDS ring of the last rows of a 64-column tile, p and log p).  At most 65535 utterances per call.
+ *
+ * fdlp_life_vae_sample (vae_sample_kernel), latentSampler: z [n_rows, bn] = mu + expf(sigma) eps in float32, the
+ * product and the sum each rounded; ml [n_rows, 2 bn] holds mu, then sigma; eps [n_rows, bn] is the caller's noise.
+ *
+ * fdlp_life_vae_elbo (vae_elbo_kernel), vae_loss per row of x, xhat [n_rows, in_dim] and ml, all sums float64:
+ *     elbo[r] = float32( (sum_k (-0.5 (x - xhat)^2 - 0.5 log(2 pi))) / in_dim
+ *                        + 0.5 ((sum_j (1 - mu^2 - exp(sigma)^2 + 2 sigma)) / bn) )
+ * (a lane of the row's wave adds k = lane, lane + 64, ..; the lanes are added by the xor butterfly 32, 16, .., 1), then
+ * per utterance, t ascending in float64, out[u ld_out] = mean_t elbo (FDLP_LIFE_LIFELONG) or mean_t expf(elbo)
+ * (FDLP_LIFE_INCREMENTAL).  elbo [n_rows] float32 is an output too.
+ *
+ * fdlp_life_fuse (lifelong_fuse_kernel): out [n_rows, C] float32 from post, w [n_utt, D] float64 and tab [D, C]
+ * float64, all arithmetic float64, i ascending from 0.0, rounded to float32 once, IEEE special values as they fall:
+ *     FDLP_LIFE_LIFELONG     out[t][c] = log(sum_i P_i[t][c] w[u][i]) - prior_weight log(sum_i tab_i[c] w[u][i]),
+ *                            tab = exp(prior)
+ *     FDLP_LIFE_INCREMENTAL  out[t][c] = (sum_i (log P_i[t][c] - prior_weight tab_i[c]) w[u][i]) / D,  tab = prior
+ * max_len: the longest utterance of the batch (it sizes the grid).  Rows of no utterance are left alone.
+ * FDLP_E_INVALID for a count outside its range or a null pointer. */
+#define FDLP_LIFE_MAX_MODELS 8
+enum { FDLP_LIFE_LIFELONG = 0, FDLP_LIFE_INCREMENTAL = 1 };
+int fdlp_life_mmeasure(const float* post_dev, int32_t n_models, int64_t n_rows, int32_t n_classes, int32_t n_utt,
+                       const int64_t* row_off_dev, const int64_t* utt_len_dev, double* out_dev, void* stream);
+int fdlp_life_vae_sample(const float* ml_dev, const float* eps_dev, float* z_dev, int64_t n_rows, int32_t bn,
+                         void* stream);
+int fdlp_life_vae_elbo(const float* x_dev, const float* xhat_dev, const float* ml_dev, int64_t n_rows, int32_t in_dim,
+                       int32_t bn, int32_t n_utt, const int64_t* row_off_dev, const int64_t* utt_len_dev, int32_t mode,
+                       float* elbo_dev, double* out_dev, int32_t ld_out, void* stream);
+int fdlp_life_fuse(const float* post_dev, int32_t n_models, int64_t n_rows, int32_t n_classes, int32_t n_utt,
+                   int64_t max_len, const int64_t* row_off_dev, const int64_t* utt_len_dev, const double* w_dev,
+                   const double* tab_dev, double prior_weight, int32_t mode, float* out_dev, void* stream);
+
 /* ApplyCmvn / ApplyCmvnReverse as two float32 vectors: out[0 .. dim) = scale, out[dim .. 2 dim) = offset, from the
  * [2, dim + 1] double stats compute-cmvn-stats writes (count = stats[dim]; count < 1 is FDLP_E_INVALID).
  * mean = s0/count; norm_vars: var = s1/count - mean^2 floored at 1e-20 (a warning on stderr), scale = 1/sqrt(var),

@@ -7,7 +7,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
 LIBDIR = os.path.join(PKG, "lib")
 LIB = os.path.join(LIBDIR, "libfdlp_hip.so")
-SOURCES = ["fdlp_dct.hip", "fdlp_autocorr.hip", "fdlp_lpc.hip", "fdlp_misc.hip", "fdlp_mfcc.hip", "fdlp_post.hip", "fdlp_nnet.hip", "fdlp_vaeenc.hip", "fdlp_plan.cpp", "fdlp_plan_feat.cpp",
+SOURCES = ["fdlp_dct.hip", "fdlp_autocorr.hip", "fdlp_lpc.hip", "fdlp_misc.hip", "fdlp_mfcc.hip", "fdlp_post.hip", "fdlp_nnet.hip", "fdlp_vaeenc.hip", "fdlp_lifelong.hip", "fdlp_plan.cpp", "fdlp_plan_feat.cpp",
            "fdlp_plan_post.cpp", "fdlp_plan_model.cpp", "fdlp_tables.cpp", "fdlp_host.cpp", "fdlp_job.cpp"]
 HEADERS = ["fdlp_internal.h", "fdlp_device.h", "fdlp_error.h", "fdlp_plan_common.h", os.path.join("..", "..", "include", "fdlp.h")]
 ARCH = os.environ.get("FDLP_OFFLOAD_ARCH", "gfx950")

@@ -138,6 +138,10 @@ class FdlpVencConfigC(ctypes.Structure):
                 ("cls_hidden", c_i32), ("n_classes", c_i32)]
 
 
+FDLP_LIFE_MAX_MODELS = 8
+FDLP_LIFE_LIFELONG, FDLP_LIFE_INCREMENTAL = 0, 1
+
+
 class FdlpPostBatchC(ctypes.Structure):
     _fields_ = [
         ("n_utt", c_i32), ("norm_mul", c_i32), ("in_dev", c_p), ("n_rows", c_i64), ("row_off", P_i64),
@@ -282,6 +286,10 @@ SIGNATURES = {
     "fdlp_venc_compute": (c_i32, [c_p, ctypes.POINTER(FdlpPostBatchC), c_i32, c_i32, c_p, ctypes.c_float, c_p]),
     "fdlp_venc_set_profiling": (c_i32, [c_p, c_i32]),
     "fdlp_venc_times": (c_i32, [c_p, P_dbl]),
+    "fdlp_life_mmeasure": (c_i32, [c_p, c_i32, c_i64, c_i32, c_i32, c_p, c_p, c_p, c_p]),
+    "fdlp_life_vae_sample": (c_i32, [c_p, c_p, c_p, c_i64, c_i32, c_p]),
+    "fdlp_life_vae_elbo": (c_i32, [c_p, c_p, c_p, c_i64, c_i32, c_i32, c_i32, c_p, c_p, c_i32, c_p, c_p, c_i32, c_p]),
+    "fdlp_life_fuse": (c_i32, [c_p, c_i32, c_i64, c_i32, c_i32, c_i64, c_p, c_p, c_p, c_p, c_dbl, c_i32, c_p, c_p]),
     "fdlp_cmvn_norm": (c_i32, [P_dbl, c_i32, c_i32, c_i32, c_i32, P_i32, c_i32, ctypes.POINTER(ctypes.c_float)]),
     "fdlp_noise_params_f64": (c_i32, [P_dbl, c_i64, P_i16, c_i64, c_dbl, c_dbl, P_i64, P_dbl]),
     "fdlp_mat_reader_open": (c_i32, [ctypes.c_char_p, ctypes.POINTER(c_p)]),

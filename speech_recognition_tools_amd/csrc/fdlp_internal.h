@@ -367,6 +367,22 @@ hipError_t launch_utt_norm(const float* in, float* out, const GruSlot* slots, in
                            hipStream_t s);
 hipError_t checks_vaeenc(unsigned int* v, bool reset);  // summed into checks_nnet
 
+// The multi-domain tools (fdlp_lifelong.hip; include/fdlp.h states the arithmetic).  row_off and utt_len are DEVICE
+// int64 [n_utt]; post is [D, n_rows, C] float32.  part: mmeasure_kernel's tile partials, 8 n_utt D mmeasure_tiles(C)
+// doubles; out [n_utt, D].
+int mmeasure_tiles(int C);
+hipError_t launch_mmeasure(const float* post, int D, int64_t n_rows, int C, int n_utt, const int64_t* row_off,
+                           const int64_t* utt_len, double* part, double* out, hipStream_t s);
+hipError_t launch_vae_sample(const float* ml, const float* eps, float* z, int64_t rows, int bn, hipStream_t s);
+// elbo [rows] float32 is written, then reduced per utterance into out[u ld] (mode 0: mean, 1: mean of expf)
+hipError_t launch_vae_elbo(const float* x, const float* xh, const float* ml, float* elbo, int64_t rows, int K, int bn,
+                           int n_utt, const int64_t* row_off, const int64_t* utt_len, int mode, double* out, int ld,
+                           hipStream_t s);
+// mode 0: lifelong (tab = exp(prior)), 1: incremental (tab = prior); max_len: the longest utterance of the batch
+hipError_t launch_lifelong_fuse(const float* post, int D, int64_t n_rows, int C, int n_utt, int64_t max_len,
+                                const int64_t* row_off, const int64_t* utt_len, const double* w, const double* tab,
+                                double pw, int mode, float* out, hipStream_t s);
+
 // One utterance of a reverb batch (fdlp_reverb): samples at pcm[off, off+T), y at [yoff, yoff+T+R-1).
 struct RevUtt {
   int64_t off, T, yoff, noff;  // noff < 0: no noise mixing

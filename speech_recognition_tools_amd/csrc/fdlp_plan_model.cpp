@@ -938,3 +938,62 @@ int fdlp_mmod_compute(fdlp_mmod_plan* p, const fdlp_post_batch* bs, int32_t tap,
                                       prior_weight, s));
   return FDLP_OK;
 }
+
+// ---------------------------------------------------------------------------------------------
+// The multi-domain tools (fdlp_lifelong.hip): stateless fronts of the four kernels; the work runs on the
+// device that is current, as the pointers belong to it
+// ---------------------------------------------------------------------------------------------
+int fdlp_life_mmeasure(const float* post, int32_t n_models, int64_t n_rows, int32_t n_classes, int32_t n_utt,
+                       const int64_t* row_off, const int64_t* utt_len, double* out, void* stream) {
+  if (n_utt < 0 || n_rows < 0) return fail(FDLP_E_INVALID, "fdlp_life_mmeasure: negative n_utt or n_rows");
+  if (n_utt == 0) return FDLP_OK;
+  if (n_models < 1 || n_models > FDLP_LIFE_MAX_MODELS || n_classes < 1 || n_utt > 65535 || !post || !row_off ||
+      !utt_len || !out)
+    return fail(FDLP_E_INVALID, "fdlp_life_mmeasure: need 1 .. " + std::to_string(FDLP_LIFE_MAX_MODELS) +
+                                    " models, n_classes >= 1, at most 65535 utterances and no null pointer (got " +
+                                    std::to_string(n_models) + " models, " + std::to_string(n_classes) + " classes, " +
+                                    std::to_string(n_utt) + " utterances)");
+  hipStream_t s = (hipStream_t)stream;
+  double* part = nullptr;  // stream-ordered scratch for the tile partials
+  const size_t n = (size_t)8 * (size_t)n_utt * (size_t)n_models * (size_t)fdlp::mmeasure_tiles(n_classes);
+  HIP_TRY(hipMallocAsync((void**)&part, sizeof(double) * n, s));
+  hipError_t e = fdlp::launch_mmeasure(post, n_models, n_rows, n_classes, n_utt, row_off, utt_len, part, out, s);
+  hipError_t e2 = hipFreeAsync(part, s);
+  if (e != hipSuccess) return fail(FDLP_E_HIP, std::string("mmeasure kernels: ") + hipGetErrorString(e));
+  if (e2 != hipSuccess) return fail(FDLP_E_HIP, std::string("hipFreeAsync: ") + hipGetErrorString(e2));
+  return FDLP_OK;
+}
+
+int fdlp_life_vae_sample(const float* ml, const float* eps, float* z, int64_t n_rows, int32_t bn, void* stream) {
+  if (n_rows < 0 || bn < 1 || (n_rows > 0 && (!ml || !eps || !z)))
+    return fail(FDLP_E_INVALID, "fdlp_life_vae_sample: need n_rows >= 0, bn >= 1 and no null pointer");
+  HIP_TRY(fdlp::launch_vae_sample(ml, eps, z, n_rows, bn, (hipStream_t)stream));
+  return FDLP_OK;
+}
+
+int fdlp_life_vae_elbo(const float* x, const float* xhat, const float* ml, int64_t n_rows, int32_t in_dim, int32_t bn,
+                       int32_t n_utt, const int64_t* row_off, const int64_t* utt_len, int32_t mode, float* elbo,
+                       double* out, int32_t ld_out, void* stream) {
+  if (n_rows < 0 || n_utt < 0 || in_dim < 1 || bn < 1 || ld_out < 1 || (mode != FDLP_LIFE_LIFELONG && mode != FDLP_LIFE_INCREMENTAL))
+    return fail(FDLP_E_INVALID, "fdlp_life_vae_elbo: need n_rows, n_utt >= 0, in_dim, bn, ld_out >= 1 and a known mode");
+  if ((n_rows > 0 && (!x || !xhat || !ml || !elbo)) || (n_utt > 0 && (!row_off || !utt_len || !out || !elbo)))
+    return fail(FDLP_E_INVALID, "fdlp_life_vae_elbo: null pointer");
+  HIP_TRY(fdlp::launch_vae_elbo(x, xhat, ml, elbo, n_rows, in_dim, bn, n_utt, row_off, utt_len, mode, out, ld_out,
+                                (hipStream_t)stream));
+  return FDLP_OK;
+}
+
+int fdlp_life_fuse(const float* post, int32_t n_models, int64_t n_rows, int32_t n_classes, int32_t n_utt,
+                   int64_t max_len, const int64_t* row_off, const int64_t* utt_len, const double* w, const double* tab,
+                   double prior_weight, int32_t mode, float* out, void* stream) {
+  if (n_utt < 0 || n_rows < 0 || max_len < 0) return fail(FDLP_E_INVALID, "fdlp_life_fuse: negative n_utt, n_rows or max_len");
+  if (n_utt == 0 || max_len == 0) return FDLP_OK;
+  if (n_models < 1 || n_models > FDLP_LIFE_MAX_MODELS || n_classes < 1 || !post || !row_off || !utt_len || !w || !tab ||
+      !out || (mode != FDLP_LIFE_LIFELONG && mode != FDLP_LIFE_INCREMENTAL))
+    return fail(FDLP_E_INVALID, "fdlp_life_fuse: need 1 .. " + std::to_string(FDLP_LIFE_MAX_MODELS) +
+                                    " models, n_classes >= 1, a known mode and no null pointer (got " +
+                                    std::to_string(n_models) + " models, " + std::to_string(n_classes) + " classes)");
+  HIP_TRY(fdlp::launch_lifelong_fuse(post, n_models, n_rows, n_classes, n_utt, max_len, row_off, utt_len, w, tab,
+                                     prior_weight, mode, out, (hipStream_t)stream));
+  return FDLP_OK;
+}
