@@ -220,6 +220,17 @@ int fdlp_set_lpc_path(fdlp_plan* plan, int32_t path);
 #define FDLP_LPC_DURBIN_LDS (-1)
 #define FDLP_LPC_DURBIN_CPLX (-2)
 int fdlp_plan_lpc_dispatch(const fdlp_plan* plan, int32_t out[6]);
+/* How the flat sweep of FDLP_AC_STRUCTURED stages D into its LDS ring.  FDLP_FLAT_AUTO (plan default): by LDS-DMA
+ * (global_load_lds_dwordx4, no staging registers) when every D row is 16-byte aligned, i.e. N is even and the
+ * plan's dct rows start aligned; otherwise through registers.  FDLP_FLAT_REGISTER forces the register form: a
+ * test switch, so that one build can compare the two (they give the same r bit for bit).  fdlp_flat_staging
+ * returns the form in use, FDLP_FLAT_REGISTER or FDLP_FLAT_DMA (host-only plans too), 0 when the plan has no
+ * VALU sweeps, or a negative error code. */
+#define FDLP_FLAT_AUTO 0
+#define FDLP_FLAT_REGISTER 1
+#define FDLP_FLAT_DMA 2
+int fdlp_set_flat_staging(fdlp_plan* plan, int32_t staging);
+int fdlp_flat_staging(const fdlp_plan* plan);
 /* DCT stage (ABI 5).  FDLP_DCT_AUTO (plan default): for the recipes' frame length N = 24000 one kernel per
  * frame (dct_frame_kernel: the packed 12000-point FFT as three in-register passes with LDS exchanges,
  * D written once); other N, and FDLP_DCT_FOUR_STEP, the two four-step kernels through the Z workspace

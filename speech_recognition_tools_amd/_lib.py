@@ -204,6 +204,8 @@ SIGNATURES = {
     "fdlp_plan_sweep_schedule": (c_i32, [c_p, c_i32, c_i32, c_p, c_p, c_p, c_i32]),
     "fdlp_set_lpc_path": (c_i32, [c_p, c_i32]),
     "fdlp_plan_lpc_dispatch": (c_i32, [c_p, P_i32]),
+    "fdlp_set_flat_staging": (c_i32, [c_p, c_i32]),
+    "fdlp_flat_staging": (c_i32, [c_p]),
     "fdlp_plan_autocorr_dispatch": (c_i32, [c_p, c_i32, P_i32]),
     "fdlp_device_checks": (c_i32, [c_p, c_p, c_p, c_i32]),
     "fdlp_set_dct_path": (c_i32, [c_p, c_i32]),

@@ -692,7 +692,8 @@ __global__ __launch_bounds__(64) void ac_wrap_kernel(DevConsts c, const double* 
 //     into C chains at each event; band j owns chain j mod C from its restart at m2_j to its
 //     emission at m1_j (C chosen on the host so that bands j and j - C never overlap).
 //     s is staged per unit in an LDS ring of 512 (+16 mirrored) positions, 128 at a time, the next
-//     128 prefetched into registers.
+//     128 prefetched into registers (skirts: s = E D is a product) or copied straight into the ring by
+//     LDS-DMA a chunk ahead (flat: s = D; see vs_dma_chunk).
 // -----------------------------------------------------------------------------------------
 
 constexpr int kVsMirror = 16;
@@ -824,8 +825,63 @@ __device__ __forceinline__ void vs_fma22(double (&acc)[A], double (&M)[A / 2], d
 // scratch and without a spill in the run loop (the register table).
 template <int A, int C>
 constexpr bool vs_fast22() { return !(A == 8 && C == 4) && !(A == 10 && C >= 6); }
-
+// Which flat instantiations have the LDS-DMA staged form (ac_vsweep_kernel<A, C, true>): those that neither gain
+// scratch nor lose a wave per SIMD by it.  That is all twelve (the staging table: 12 to 15 VGPRs fewer
+// each, and <10, 8> goes from 88 to 24 bytes of scratch).
 template <int A, int C>
+constexpr bool vs_flat_dma() { return C > 0; }
+
+// LDS-DMA staging of the flat sweep (DMA, C > 0 only).  The flat signal is D itself, so a 128-position chunk of
+// frame row r is 128 contiguous doubles of its D row and lands in 128 contiguous ring slots: one
+// global_load_lds_dwordx4 per row (64 lanes x 16 B = 1 KB), four per chunk, where the register form spends 8
+// loads, 8 ds_writes, their clamps, slot arithmetic and selects, and holds pf (16 VGPRs) for a whole chunk.
+// The row bases are wave-uniform (scalar base, one 32-bit lane offset shared by the four rows).  The copies
+// are issued from one asm statement that writes M0 and restores it: the compiler neither sees nor counts them
+// (with the builtin it drains vmcnt(0) before the next LDS access, and the sweep reads LDS every block, DESIGN
+// 6 r04z).  Order, per chunk (ensure): arrival of chunk [lo, lo + 128) = s_waitcnt vmcnt(0), then
+// wave_lds_sync(), then the edge zeros and the mirror copy, flush(), the next chunk's copies, wave_lds_sync().
+//   RAW: a staged range is read only behind the vmcnt(0) that retires its copies and the wave_lds_sync() after
+//        it (one wave per block, so the wave barrier is the barrier); vmcnt(0) also covers flush()'s stores,
+//        which are a whole chunk old like the copies.
+//   WAR: the copies issued when the staged range starts at lo target the slots of [lo - 128, lo), which are
+//        those of [lo + 384, lo + 512).  The highest position still to be read is that of the block at the head
+//        of which ensure() runs: below lo + 128 + 17 A - 1 (vs_dma_war_ok); every earlier read of those slots
+//        is several blocks old and behind the lgkmcnt(0) of each block since.
+// Rows need 16-byte alignment: the host picks this form only for even N and an aligned dct base.
+template <int A>
+constexpr bool vs_dma_war_ok() {
+  return vs_chunk_positions(A, true) + 17 * A - 1 <= kVsRingPositions - vs_chunk_positions(A, true);
+}
+// the four rows' copies of one chunk: lane i of row r copies the 16 bytes at row[r] + off (off = each lane's
+// byte offset into the row, the same for the four rows) to LDS byte address lds0 + r * row_bytes + 16 i.
+// Wait states the compiler does not insert inside the string: s_nop 4 ahead of the first copy (its scalar
+// operands may have just been written by the SALU), s_nop 0 between a write of M0 and the copy that reads it.
+template <int ROWB>
+__device__ __forceinline__ void vs_dma_chunk(const double* r0, const double* r1, const double* r2, const double* r3,
+                                             uint32_t off, uint32_t lds0) {
+  uint32_t keep;
+  asm volatile(
+      "s_nop 4\n\t"
+      "s_mov_b32 %0, m0\n\t"
+      "s_mov_b32 m0, %6\n\t"
+      "s_nop 0\n\t"
+      "global_load_lds_dwordx4 %1, %2\n\t"
+      "s_add_u32 m0, m0, %7\n\t"
+      "s_nop 0\n\t"
+      "global_load_lds_dwordx4 %1, %3\n\t"
+      "s_add_u32 m0, m0, %7\n\t"
+      "s_nop 0\n\t"
+      "global_load_lds_dwordx4 %1, %4\n\t"
+      "s_add_u32 m0, m0, %7\n\t"
+      "s_nop 0\n\t"
+      "global_load_lds_dwordx4 %1, %5\n\t"
+      "s_mov_b32 m0, %0"
+      : "=&s"(keep)
+      : "v"(off), "s"(r0), "s"(r1), "s"(r2), "s"(r3), "s"(lds0), "n"(ROWB)
+      : "memory", "scc");
+}
+
+template <int A, int C, bool DMA = false>
 __global__ __launch_bounds__(64, vs_waves_per_simd<C>()) void ac_vsweep_kernel(DevConsts c, const double* __restrict__ dct,
                                                           double* __restrict__ rlow, double* __restrict__ rup,
                                                           double* __restrict__ rflat,
@@ -857,8 +913,11 @@ __global__ __launch_bounds__(64, vs_waves_per_simd<C>()) void ac_vsweep_kernel(D
   // row stride 544 doubles = 17 x 256 B: each ds_read_b128 lane group (lanes 0-3,12-15 of one row and
   // 4-11 of the next, MI355X_MICROARCH.md LDS) then covers the 64 banks exactly with the 10-double lane
   // stride of the window reads (A = 10; a 528 stride measured 9.4e7 conflict cycles per launch)
-  __shared__ double ring_all[4][kRow];
+  __shared__ __attribute__((aligned(16))) double ring_all[4][kRow];
   static_assert(kVsMirror <= 32, "mirror fits the row padding");
+  static_assert(!DMA || C > 0, "LDS-DMA staging: the flat sweep only (the skirt sweeps stage E D, a product)");
+  static_assert(!DMA || (vs_dma_war_ok<A>() && kVsChunk == 128 && (kRow * sizeof(double)) % 16 == 0),
+                "LDS-DMA staging: a chunk is one 1 KB copy per row, 16-byte aligned, above every read still to come");
   // C == 0: the two skirt sweeps, item = 2 group + skirt (a frame group's two sweeps adjacent on one
   // XCD, so its D rows are read from HBM once); C > 0: the flat-top sweep, item = group
   // (C > 0: item = H group + part, the parts of a frame group adjacent on one XCD)
@@ -907,7 +966,7 @@ __global__ __launch_bounds__(64, vs_waves_per_simd<C>()) void ac_vsweep_kernel(D
 
   // ---- staging: value at sweep position n, prefetched 128 positions ahead ----------------------
   constexpr int kPf = kVsChunk / 16;
-  double pf[kPf], pe[C == 0 ? kPf : 1];
+  double pf[DMA ? 1 : kPf], pe[C == 0 ? kPf : 1];  // DMA: no staging registers
   // unconditional (clamped) loads: no branches around them, and their registers are read only in
   // commit, one chunk later, so the wait for them is not pulled into the FMA loop
   // A skirt-sweep chunk that lies inside [0, N) (every chunk but the sweep's first and last) needs no clamping
@@ -918,8 +977,32 @@ __global__ __launch_bounds__(64, vs_waves_per_simd<C>()) void ac_vsweep_kernel(D
   // registers, spills with the second copy: 0.90 -> 1.18 ms; it keeps the general form.)
   static_assert((kVsRing & (kVsRing - 1)) == 0 && kVsRing % kVsChunk == 0 && kVsMirror == 16, "aligned chunk runs");
   auto inside = [&](int base) { return C == 0 && base >= 0 && base + kVsChunk <= N; };
+  // DMA: the four rows of the wave (row 0 again for the frames past the batch's end, as drow)
+  const double* dma_row[4] = {nullptr, nullptr, nullptr, nullptr};
+  if constexpr (DMA) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int fr = 4 * g + r < nframes ? 4 * g + r : 0;
+      FDLP_CHECK(fr >= 0 && fr < nframes);
+      dma_row[r] = dct + (int64_t)fr * N;
+    }
+  }
   auto issue = [&](int base) __attribute__((always_inline)) {
-    if (inside(base)) {  // wave-uniform
+    if constexpr (DMA) {
+      // A chunk below position 0 is never staged (lo_loaded >= 0) and one at or above N is all zeros, written
+      // at its arrival: neither is fetched.  A chunk that reaches past N (the sweep's first ones; N need not
+      // be a multiple of the chunk) reads the row's last pair again for its lanes at or above N, inside the
+      // row, and those slots are zeroed at arrival.
+      if (base < 0 || base >= N) return;  // wave-uniform
+      const int sb = base & (kVsRing - 1);
+      const int m = min(base + 2 * lane, N - 2);
+      FDLP_CHECK((N & 1) == 0 && m >= 0 && m + 2 <= N && (m & 1) == 0);        // source: inside the row, 16-byte aligned
+      FDLP_CHECK(sb >= 0 && sb + kVsChunk <= kVsRing && sb % kVsChunk == 0);  // destination: inside the ring
+      const uint32_t lds0 = (uint32_t)(uintptr_t)((__attribute__((address_space(3))) double*)(&ring_all[0][0] + sb));
+      vs_dma_chunk<kRow * (int)sizeof(double)>(dma_row[0], dma_row[1], dma_row[2], dma_row[3],
+                                               (uint32_t)m * (uint32_t)sizeof(double),
+                                               __builtin_amdgcn_readfirstlane(lds0));
+    } else if (inside(base)) {  // wave-uniform
       if (kind == 0) {
         const double* pd = drow + (N - 1 - base - l);
         const double* pw = ew + (N - 1 - base - l);
@@ -948,7 +1031,26 @@ __global__ __launch_bounds__(64, vs_waves_per_simd<C>()) void ac_vsweep_kernel(D
     }
   };
   auto commit = [&](int base) __attribute__((always_inline)) {
-    if (inside(base)) {  // wave-uniform
+    if constexpr (DMA) {
+      // arrival: where the register form waits for pf
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      wave_lds_sync();
+      FDLP_CHECK(base >= 0 && base % kVsChunk == 0);
+      const int sb = base & (kVsRing - 1);
+      if (base + kVsChunk > N) {  // wave-uniform: the positions at or above N are zeros
+#pragma unroll
+        for (int q = 0; q < kPf; ++q) {
+          const int n = base + 16 * q + l;
+          FDLP_CHECK(sb + 16 * q + l < kVsRing);
+          if (n >= N) rg[sb + 16 * q + l] = 0.0;
+        }
+        wave_lds_sync();
+      }
+      if (sb == 0) {  // wave-uniform: the chunk at slot 0 fills the mirror behind the ring
+        FDLP_CHECK(kVsRing + l < kVsRing + kVsMirror && kVsRing + kVsMirror <= kRow);
+        rg[kVsRing + l] = rg[l];
+      }
+    } else if (inside(base)) {  // wave-uniform
       const int sb = base & (kVsRing - 1);
       double* w = rg + sb + l;
 #pragma unroll
@@ -992,6 +1094,8 @@ __global__ __launch_bounds__(64, vs_waves_per_simd<C>()) void ac_vsweep_kernel(D
   // right after the ring commit and before the next prefetch.  A VMEM store's data registers must
   // not be rewritten before the store completes (vmcnt, in order with the prefetch loads), so storing
   // from reused registers would put a wait for the prefetch at the head of every block.
+  // (a second parked row in the DMA form, which has the registers for it -- <10, 5> 229 -> 249 VGPRs -- measured
+  // 0.708-0.736 -> 0.716-0.744 ms: not kept, r10a)
   constexpr int P = C == 0 ? 2 : 1;
   double* const outb = kind == 0 ? rlow : (kind == 1 ? rup : rflat);
   double pend[P][A];
@@ -1326,6 +1430,29 @@ bool vsweep_fast22(int A, int C) {
   }
 }
 
+// vs_flat_dma<A, C>() for run-time A, C
+template <int A>
+static bool vs_flat_dma_chains(int C) {
+  switch (C) {
+    case 4: return vs_flat_dma<A, 4>();
+    case 5: return vs_flat_dma<A, 5>();
+    case 6: return vs_flat_dma<A, 6>();
+    case 8: return vs_flat_dma<A, 8>();
+    default: return false;
+  }
+}
+// The flat sweep's staging: LDS-DMA where the instantiation has that form, the plan does not force the register
+// form (fdlp_set_flat_staging), and every D row is 16-byte aligned (even N, aligned base).
+bool vsweep_flat_dma(int A, int C, int N, int fl_stage, const void* dct) {
+  if (fl_stage == 1 || (N & 1) != 0 || ((uintptr_t)dct & 15) != 0) return false;
+  switch (A) {
+    case 4: return vs_flat_dma_chains<4>(C);
+    case 8: return vs_flat_dma_chains<8>(C);
+    case 10: return vs_flat_dma_chains<10>(C);
+    default: return false;
+  }
+}
+
 template <int A, int C>
 static hipError_t launch_vsweep_ac(const DevConsts& c, const double* dct, int nframes, double* r, double* rup,
                                    double* rflat, double* rpart, hipStream_t s) {
@@ -1333,6 +1460,14 @@ static hipError_t launch_vsweep_ac(const DevConsts& c, const double* dct, int nf
   hipLaunchKernelGGL((ac_vsweep_kernel<A, 0>), dim3(xcd_grid(2 * ngroups)), dim3(64), 0, s, c, dct, r, rup, rflat,
                      rpart, c.sk_snap, c.fl_ev, nframes, ngroups);
   (void)kmark(kKVsweepSkirt, s);
+  if constexpr (vs_flat_dma<A, C>()) {
+    if (vsweep_flat_dma(A, C, c.N, c.fl_stage, dct)) {
+      hipLaunchKernelGGL((ac_vsweep_kernel<A, C, true>), dim3(xcd_grid(c.fl_H * ngroups)), dim3(64), 0, s, c, dct, r,
+                         rup, rflat, rpart, c.sk_snap, c.fl_ev, nframes, ngroups);
+      (void)kmark(kKVsweepFlat, s);
+      return hipGetLastError();
+    }
+  }
   hipLaunchKernelGGL((ac_vsweep_kernel<A, C>), dim3(xcd_grid(c.fl_H * ngroups)), dim3(64), 0, s, c, dct, r, rup,
                      rflat, rpart, c.sk_snap, c.fl_ev, nframes, ngroups);
   (void)kmark(kKVsweepFlat, s);

@@ -119,6 +119,7 @@ struct DevConsts {
   int fl_H = 1;
   int fl_part_lo[kMaxFlatParts] = {0}, fl_part_hi[kMaxFlatParts] = {0}, fl_part_ev[kMaxFlatParts + 1] = {0};
   const int2* fl_band = nullptr;  // [B] (chain, bitmask of the parts h < fl_H - 1 it needs a partial from)
+  int fl_stage = 0;               // fdlp_set_flat_staging: 0 LDS-DMA where it applies (default), 1 the register form
   // wrap straddle shared by the bands whose first / last nlags - 1 taps lie on their skirts: [B]
   // sqrt(K_j K'_j), 0 for the bands whose wrap straddle ac_band_kernel computes from the taps; null: none
   const double* sk_wrap = nullptr;
@@ -186,6 +187,9 @@ hipError_t launch_autocorr_structured(const DevConsts& c, const double* dct, int
 int vsweep_lanes_lags(int nlags);   // lags per lane of ac_vsweep_kernel, 0 = unsupported
 int vsweep_chains(int C);           // chain count instantiated for C needed chains, 0 = unsupported
 bool vsweep_fast22(int A, int C);   // vs_fast22<A, C>(): the sweep's plain runs in the 2x2 fast-correlation form (C = 0: skirts)
+// the flat sweep <A, C> stages its chunks by LDS-DMA (else through registers): the instantiation has that form,
+// fl_stage (DevConsts) does not force the register form, N is even and the D rows' base is 16-byte aligned
+bool vsweep_flat_dma(int A, int C, int N, int fl_stage, const void* dct);
 // What the autocorrelation stage launches on the resolved path (1 direct, 2 structured, 3 structured_mfma), from
 // the launchers' own dispatch functions (no device needed): out as fdlp_plan_autocorr_dispatch documents it.
 // reg [B] (m1, m2); wrap_kw [B] the shared-wrap factors, null when the plan has none.

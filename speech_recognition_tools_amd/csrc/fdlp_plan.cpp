@@ -872,6 +872,22 @@ int fdlp_set_lpc_path(fdlp_plan* p, int32_t path) {
   return FDLP_OK;
 }
 
+int fdlp_set_flat_staging(fdlp_plan* p, int32_t staging) {
+  if (!p || (staging != FDLP_FLAT_AUTO && staging != FDLP_FLAT_REGISTER))
+    return fail(FDLP_E_INVALID, "fdlp_set_flat_staging: need a plan and FDLP_FLAT_AUTO or FDLP_FLAT_REGISTER");
+  p->dc.fl_stage = staging;
+  return FDLP_OK;
+}
+
+int fdlp_flat_staging(const fdlp_plan* p) {
+  if (!p) return fail(FDLP_E_INVALID, "fdlp_flat_staging: null plan");
+  if (!p->sk_avail || !p->vs_avail) return 0;
+  // the launcher's own rule (launch_vsweep_ac); every sub-batch's rows start a whole number of rows behind ws.dct
+  const bool dma = fdlp::vsweep_flat_dma(fdlp::vsweep_lanes_lags(p->nlags), fdlp::vsweep_chains(p->sk.fl_C), p->N,
+                                         p->dc.fl_stage, p->device < 0 ? nullptr : p->ws.dct);
+  return dma ? FDLP_FLAT_DMA : FDLP_FLAT_REGISTER;
+}
+
 int fdlp_plan_lpc_dispatch(const fdlp_plan* p, int32_t out[6]) {
   if (!p || !out) return fail(FDLP_E_INVALID, "fdlp_plan_lpc_dispatch: need a plan and out[6]");
   if (p->cplx) {  // cplx_lpc_out_kernel (launch_cplx_modspec), not launch_lpc_env

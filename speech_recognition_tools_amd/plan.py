@@ -194,6 +194,20 @@ class FdlpPlan:
                             fast22_skirt=bool(fs), fast22_flat=bool(ff), wrap_shared=bool(wrap), fast_bands=fast)
         return res
 
+    FLAT_STAGINGS = {"auto": 0, "register": 1}
+
+    def set_flat_staging(self, staging: str = "auto"):
+        """'auto': the flat sweep stages D into its LDS ring by LDS-DMA where the rows are 16-byte aligned
+        (even N); 'register': the register-staged form everywhere (a test switch: same r, bit for bit)."""
+        check(lib.fdlp_set_flat_staging(self._h, self.FLAT_STAGINGS[staging]))
+
+    @property
+    def flat_staging(self):
+        """'dma' or 'register': the flat sweep's staging in use; None when the plan has no VALU sweeps."""
+        v = lib.fdlp_flat_staging(self._h)
+        check(v if v < 0 else 0)
+        return {0: None, 1: "register", 2: "dma"}[v]
+
     LPC_PATHS = {"auto": 0, "lds": 1, "lattice8": 2}
 
     def set_lpc_path(self, path: str = "auto"):
