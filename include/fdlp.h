@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define FDLP_ABI_VERSION 12
+#define FDLP_ABI_VERSION 13
 
 enum {
   FDLP_OK = 0,
@@ -458,6 +458,16 @@ int fdlp_xform_plan_destroy(fdlp_xform_plan* plan);
  * tile; LDS bytes of a workgroup.  Works on a host-only plan (post.device = -1).  Any pointer may be NULL. */
 int fdlp_xform_plan_info(const fdlp_xform_plan* plan, int32_t* in_dim, int32_t* out_dim, int32_t* mat_cols,
                          int32_t* tile, int32_t* lds_bytes);
+/* What a compute call of this plan launches, from the function the launcher itself selects by:
+ *   info[0] mode     delta stage of the code object: -1 none, 0 any order and window, 1 and 2 = that order at window 2
+ *   info[1] ncb      16-column blocks of the result a wave accumulates at once: min(ceil(out_dim / 16), 4)
+ *   info[2] groups   column groups of 16 ncb the kernel loops over
+ *   info[3] tile     frames per workgroup
+ *   info[4] vec      1: the rows are read from LDS 16 bytes at a time (D (order + 1) a multiple of 4)
+ *   info[5], [6]     K = 32 info[5] + info[6]: full chunks of the staged matrix, and the length of the tail chunk
+ *   info[7]          1: the launch asks for more than 64 KB of dynamic LDS and raises the kernel's limit first
+ * xform_kernel<mode, ncb> is one of 16 code objects.  Works on a host-only plan. */
+int fdlp_xform_plan_dispatch(const fdlp_xform_plan* plan, int32_t info[8]);
 /* `batch` as for fdlp_post_compute, except that out_dev is [n_rows, out_dim].  mat_dev: device table
  * [n_mat, out_dim, mat_cols] of float32; mat_index[u] (host, or NULL = matrix 0) picks utterance u's matrix, so
  * per-speaker fMLLR shares the launch. */

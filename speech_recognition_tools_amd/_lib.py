@@ -40,7 +40,7 @@ FDLP_MODE_MODSPEC_COMPLEX = 2
 FDLP_WIN_HAMMING = 0
 FDLP_WIN_HANNING = 1
 FDLP_WIN_RECT = 2
-ABI_VERSION = 12
+ABI_VERSION = 13
 FDLP_FN_LOG, FDLP_FN_EXP = 0, 1  # fdlp_device_fn
 STAGE_NAMES = ("frames_dft1", "dft2_dct", "autocorr", "lpc_env", "ola_log")
 
@@ -258,6 +258,7 @@ SIGNATURES = {
     "fdlp_xform_plan_create": (c_i32, [ctypes.POINTER(FdlpXformConfigC), ctypes.POINTER(c_p)]),
     "fdlp_xform_plan_destroy": (c_i32, [c_p]),
     "fdlp_xform_plan_info": (c_i32, [c_p, P_i32, P_i32, P_i32, P_i32, P_i32]),
+    "fdlp_xform_plan_dispatch": (c_i32, [c_p, P_i32]),
     "fdlp_xform_compute": (c_i32, [c_p, ctypes.POINTER(FdlpPostBatchC), c_p, c_i32, P_i32, c_p]),
     "fdlp_nnet_plan_create": (c_i32, [ctypes.POINTER(FdlpNnetConfigC), ctypes.POINTER(c_p), ctypes.POINTER(c_p), c_i64,
                                       ctypes.POINTER(c_p)]),

@@ -307,6 +307,18 @@ hipError_t launch_xform(const PostConsts& c, XformConsts xc, const PostTile* til
                         int64_t n_rows, const float* norm, int norm_mul, const float* mats, float* out,
                         hipStream_t s);
 size_t xform_ms_bytes(int N);  // LDS bytes of the staged matrix chunk
+int post_mode(int order, int window);  // MODE of post_kernel / xform_kernel: -1 no deltas, 0 general, 1, 2 at window 2
+// The launch launch_xform makes for a plan (it reads this struct itself) and the branches xform_stage then takes.
+struct XformDispatch {
+  int mode, ncb;          // xform_kernel<mode, ncb>
+  int groups;             // column groups of 16 ncb the kernel loops over
+  int tile;               // frames per workgroup
+  int vec;                // 16-byte LDS loads of the rows (D' a multiple of 4)
+  int full_chunks, tail;  // K = 32 full_chunks + tail
+  int big_lds;            // the launch raises the kernel's dynamic LDS limit first
+  size_t post_lds, lds;   // bytes of the two tiles, and with the staged matrix chunk
+};
+XformDispatch xform_dispatch(const PostConsts& c, int N);
 size_t xform_lds_bytes(int tf, int D, int order, int window, int L, int R, int N);
 hipError_t checks_post(unsigned int* v, bool reset);
 

@@ -192,6 +192,14 @@ int fdlp_xform_plan_info(const fdlp_xform_plan* x, int32_t* in_dim, int32_t* out
   return FDLP_OK;
 }
 
+int fdlp_xform_plan_dispatch(const fdlp_xform_plan* x, int32_t info[8]) {
+  if (!x || !info) return fail(FDLP_E_INVALID, "fdlp_xform_plan_dispatch: null argument");
+  const fdlp::XformDispatch d = fdlp::xform_dispatch(x->post->pc, x->N);
+  info[0] = d.mode; info[1] = d.ncb; info[2] = d.groups; info[3] = d.tile;
+  info[4] = d.vec; info[5] = d.full_chunks; info[6] = d.tail; info[7] = d.big_lds;
+  return FDLP_OK;
+}
+
 int fdlp_xform_compute(fdlp_xform_plan* x, const fdlp_post_batch* b, const void* mat_dev, int32_t n_mat,
                        const int32_t* mat_index, void* stream) {
   if (!x || !b) return fail(FDLP_E_INVALID, "fdlp_xform_compute: null argument");

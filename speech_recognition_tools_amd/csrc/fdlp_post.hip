@@ -22,6 +22,7 @@ namespace fdlp {
 constexpr int kPostThreads = 256;
 constexpr int kPostLdsMax = 160 * 1024;
 constexpr int kPostLdsTarget = 64 * 1024;  // two workgroups per CU: one loads while the other stores
+constexpr size_t kPostLdsNoAttr = 64 * 1024;  // dynamic LDS a launch may ask for without raising the kernel's limit
 constexpr int kPostTileMax = 128;
 constexpr int kXfKC = 32;         // columns k of the transform staged in LDS at a time
 constexpr int kXfColBlocks = 4;   // 16-column blocks of the result a wave accumulates at once
@@ -440,19 +441,26 @@ __global__ __launch_bounds__(kPostThreads) void xform_kernel(PostConsts c, Xform
   post_body<MODE, NCB>(c, tiles, x, n_rows, norm, norm_mul, out, xc, mats);
 }
 
+// the delta stage's code object: post_kernel<MODE> and xform_kernel<MODE, NCB> are picked by this and nothing else
+int post_mode(int order, int window) {
+  return order == 0 ? -1 : (window == kPostSpecWindow && order <= kPostSpecMax ? order : 0);
+}
+
 hipError_t launch_post(const PostConsts& c, const PostTile* tiles, int ntiles, const float* x, int64_t n_rows,
                        const float* norm, int norm_mul, float* out, hipStream_t s) {
   if (ntiles <= 0) return hipSuccess;
   const size_t lds = post_lds_bytes(c.tf, c.D, c.order, c.window, c.L, c.R);
-  const int mode = c.order == 0 ? -1 : (c.window == kPostSpecWindow && c.order <= kPostSpecMax ? c.order : 0);
-#define FDLP_POST_LAUNCH(M)                                                                                        \
-  do {                                                                                                             \
-    if (lds > 65536)                                                                                               \
-      (void)hipFuncSetAttribute((const void*)post_kernel<M>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    hipLaunchKernelGGL(post_kernel<M>, dim3(ntiles), dim3(kPostThreads), lds, s, c, tiles, x, n_rows, norm,        \
-                       norm_mul, out);                                                                             \
+#define FDLP_POST_LAUNCH(M)                                                                                       \
+  do {                                                                                                            \
+    if (lds > kPostLdsNoAttr) {                                                                                   \
+      const hipError_t e = hipFuncSetAttribute((const void*)post_kernel<M>,                                       \
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);             \
+      if (e != hipSuccess) return e;                                                                              \
+    }                                                                                                             \
+    hipLaunchKernelGGL(post_kernel<M>, dim3(ntiles), dim3(kPostThreads), lds, s, c, tiles, x, n_rows, norm,       \
+                       norm_mul, out);                                                                            \
   } while (0)
-  switch (mode) {
+  switch (post_mode(c.order, c.window)) {
     case -1: FDLP_POST_LAUNCH(-1); break;
     case 1: FDLP_POST_LAUNCH(1); break;
     case 2: FDLP_POST_LAUNCH(2); break;
@@ -462,20 +470,39 @@ hipError_t launch_post(const PostConsts& c, const PostTile* tiles, int ntiles, c
   return hipGetLastError();
 }
 
+// What launch_xform runs for a plan: the template arguments and the branches xform_stage takes.  The launcher
+// reads its template arguments, the LDS size and the attribute decision from here, and fdlp_xform_plan_dispatch
+// reports the same struct, so the report cannot describe another launch than the one that runs.
+XformDispatch xform_dispatch(const PostConsts& c, int N) {
+  XformDispatch d;
+  d.mode = post_mode(c.order, c.window);
+  d.ncb = xform_ncb(N);
+  d.groups = (N + 16 * d.ncb - 1) / (16 * d.ncb);
+  d.tile = c.tf;
+  d.vec = (c.Dp & 3) == 0;
+  d.full_chunks = c.Dout / kXfKC;
+  d.tail = c.Dout % kXfKC;
+  d.post_lds = post_lds_bytes(c.tf, c.D, c.order, c.window, c.L, c.R);
+  d.lds = d.post_lds + xform_ms_bytes(N);
+  d.big_lds = d.lds > kPostLdsNoAttr;
+  return d;
+}
+
 template <int NCB>
 static hipError_t launch_xform_ncb(const PostConsts& c, const XformConsts& xc, const PostTile* tiles, int ntiles,
                                    const float* x, int64_t n_rows, const float* norm, int norm_mul,
-                                   const float* mats, float* out, size_t lds, hipStream_t s) {
-  const int mode = c.order == 0 ? -1 : (c.window == kPostSpecWindow && c.order <= kPostSpecMax ? c.order : 0);
-#define FDLP_XFORM_LAUNCH(M)                                                                                  \
-  do {                                                                                                        \
-    if (lds > 65536)                                                                                          \
-      (void)hipFuncSetAttribute((const void*)xform_kernel<M, NCB>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                (int)lds);                                                                    \
-    hipLaunchKernelGGL((xform_kernel<M, NCB>), dim3(ntiles), dim3(kPostThreads), lds, s, c, xc, tiles, x,     \
-                       n_rows, norm, norm_mul, mats, out);                                                    \
+                                   const float* mats, float* out, const XformDispatch& d, hipStream_t s) {
+#define FDLP_XFORM_LAUNCH(M)                                                                                    \
+  do {                                                                                                          \
+    if (d.big_lds) {                                                                                            \
+      const hipError_t e = hipFuncSetAttribute((const void*)xform_kernel<M, NCB>,                               \
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)d.lds);         \
+      if (e != hipSuccess) return e;                                                                            \
+    }                                                                                                           \
+    hipLaunchKernelGGL((xform_kernel<M, NCB>), dim3(ntiles), dim3(kPostThreads), d.lds, s, c, xc, tiles, x,     \
+                       n_rows, norm, norm_mul, mats, out);                                                      \
   } while (0)
-  switch (mode) {
+  switch (d.mode) {
     case -1: FDLP_XFORM_LAUNCH(-1); break;
     case 1: FDLP_XFORM_LAUNCH(1); break;
     case 2: FDLP_XFORM_LAUNCH(2); break;
@@ -493,14 +520,13 @@ hipError_t launch_xform(const PostConsts& c, XformConsts xc, const PostTile* til
                         int64_t n_rows, const float* norm, int norm_mul, const float* mats, float* out,
                         hipStream_t s) {
   if (ntiles <= 0) return hipSuccess;
-  const size_t plds = post_lds_bytes(c.tf, c.D, c.order, c.window, c.L, c.R);
-  const size_t lds = plds + xform_ms_bytes(xc.N);
-  xc.ms_off = (int)(plds / sizeof(float));
-  switch (xform_ncb(xc.N)) {
-    case 1: return launch_xform_ncb<1>(c, xc, tiles, ntiles, x, n_rows, norm, norm_mul, mats, out, lds, s);
-    case 2: return launch_xform_ncb<2>(c, xc, tiles, ntiles, x, n_rows, norm, norm_mul, mats, out, lds, s);
-    case 3: return launch_xform_ncb<3>(c, xc, tiles, ntiles, x, n_rows, norm, norm_mul, mats, out, lds, s);
-    default: return launch_xform_ncb<4>(c, xc, tiles, ntiles, x, n_rows, norm, norm_mul, mats, out, lds, s);
+  const XformDispatch d = xform_dispatch(c, xc.N);
+  xc.ms_off = (int)(d.post_lds / sizeof(float));
+  switch (d.ncb) {
+    case 1: return launch_xform_ncb<1>(c, xc, tiles, ntiles, x, n_rows, norm, norm_mul, mats, out, d, s);
+    case 2: return launch_xform_ncb<2>(c, xc, tiles, ntiles, x, n_rows, norm, norm_mul, mats, out, d, s);
+    case 3: return launch_xform_ncb<3>(c, xc, tiles, ntiles, x, n_rows, norm, norm_mul, mats, out, d, s);
+    default: return launch_xform_ncb<4>(c, xc, tiles, ntiles, x, n_rows, norm, norm_mul, mats, out, d, s);
   }
 }
 

@@ -186,6 +186,18 @@ class XformPlan:
     def __del__(self):
         self.close()
 
+    def dispatch(self) -> dict:
+        """What compute() launches, read from the function the launcher selects by: xform_kernel<mode, ncb>
+        (mode -1 no deltas, 0 general, 1 and 2 = that order at window 2), the column `groups` of 16 ncb, the `tile`,
+        `vec` (16-byte LDS reads of the rows), K = 32 full_chunks + tail, and big_lds (more than 64 KB of dynamic
+        LDS).  Works on a host-only plan."""
+        info = (_lib.c_i32 * 8)()
+        check(lib.fdlp_xform_plan_dispatch(self._h, info))
+        keys = ("mode", "ncb", "groups", "tile", "vec", "full_chunks", "tail", "big_lds")
+        d = dict(zip(keys, (int(v) for v in info)))
+        d["vec"], d["big_lds"] = bool(d["vec"]), bool(d["big_lds"])
+        return d
+
     def compute(self, feats: torch.Tensor, lengths: Sequence[int], mats: torch.Tensor,
                 mat_index: Optional[Sequence[int]] = None, norm: Optional[torch.Tensor] = None,
                 norm_index: Optional[Sequence[int]] = None, norm_vars: bool = True,

@@ -270,7 +270,7 @@ def test_entry_points_are_declared_and_exported():
     declared = set(re.findall(r"\b(fdlp_[a-z0-9_]+)\s*\(", src))
     for n in names:
         assert n in declared and n in _lib.SIGNATURES and hasattr(_lib.lib, n), n
-    assert "#define FDLP_ABI_VERSION 12" in src and _lib.lib.fdlp_abi_version() == 12
+    assert "#define FDLP_ABI_VERSION 13" in src and _lib.lib.fdlp_abi_version() == 13
     p = NnetPlan(PostConfig(dim=4), None, None, device=-1, dims=[4, 3])
     with pytest.raises(_lib.FdlpError):                                  # a host-only plan refuses to compute
         _lib.check(_lib.lib.fdlp_nnet_compute(p._h, ctypes.byref(_lib.FdlpPostBatchC()), 0, 0, None, 0.8, None))

@@ -212,6 +212,22 @@ SHAPES = [(1, 0, 2, 0, 0, 0), (1, 2, 2, 4, 4, 0), (1, 3, 3, 3, 0, 0), (13, 2, 2,
           (13, 3, 3, 0, 2, 0), (13, 0, 2, 4, 4, 0), (80, 2, 2, 4, 4, 0), (80, 0, 2, 3, 0, 0), (80, 1, 1, 0, 0, 0),
           (80, 0, 2, 0, 0, 0), (80, 3, 3, 0, 2, 0),
           (13, 1, 2, 0, 0, 0), (80, 3, 2, 1, 1, 0)]  # window 2: the order-1 kernel, and order 3 on the general one
+# rows too wide for 16 frames per tile: shape -> (tile, LDS bytes) of the plain chain.  One frame per tile above 64 KB
+# (the launch raises the kernel's dynamic LDS limit first) in each of post_kernel's four code objects, and tiles 2, 4, 8
+SMALL_TILES = {(440, 2, 2, 4, 4, 0): (1, 77440), (600, 0, 2, 16, 15, 0): (1, 76800), (450, 1, 1, 10, 10, 0): (1, 117008),
+               (350, 1, 2, 8, 8, 0): (1, 77008), (400, 2, 2, 3, 3, 0): (2, 64000), (333, 1, 2, 5, 4, 0): (4, 57288),
+               (120, 2, 2, 10, 10, 0): (8, 57600)}
+SHAPES += list(SMALL_TILES)
+
+
+def test_small_tile_shapes_have_their_tiles():
+    from speech_recognition_tools_amd.post import PostConfig, PostPlan
+    for (D, order, window, L, R, truncate), want in SMALL_TILES.items():
+        p = PostPlan(PostConfig(dim=D, truncate=truncate, delta_order=order, delta_window=window, left_context=L,
+                                right_context=R), device=-1)
+        assert (p.tile, p.lds_bytes) == want, (D, order, window, L, R)
+    assert sorted(t for t, _ in SMALL_TILES.values()) == [1, 1, 1, 1, 2, 4, 8]
+    assert sum(b > 65536 for _, b in SMALL_TILES.values()) == 4
 
 
 @pytest.mark.gpu

@@ -355,7 +355,7 @@ def test_entry_points_are_declared_and_exported():
     declared = set(re.findall(r"\b(fdlp_[a-z0-9_]+)\s*\(", src))
     for n in names:
         assert n in declared and n in _lib.SIGNATURES and hasattr(_lib.lib, n), n
-    assert "#define FDLP_ABI_VERSION 12" in src and _lib.lib.fdlp_abi_version() == 12
+    assert "#define FDLP_ABI_VERSION 13" in src and _lib.lib.fdlp_abi_version() == 13
     assert "#define FDLP_RNN_MAX_STAGES 32" in src and _lib.FDLP_RNN_MAX_STAGES == 32
     p = RnnPlan(PostConfig(dim=4), None, device=-1, kinds=["gru"], dims=[4, 3])
     with pytest.raises(_lib.FdlpError, match="host-only"):               # a host-only plan refuses to compute

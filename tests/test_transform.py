@@ -202,13 +202,14 @@ def test_capacity_and_argument_refusals():
 def test_new_entry_points_are_declared_and_exported():
     import re
     from speech_recognition_tools_amd import _lib
-    names = ["fdlp_xform_plan_create", "fdlp_xform_plan_destroy", "fdlp_xform_plan_info", "fdlp_xform_compute"]
+    names = ["fdlp_xform_plan_create", "fdlp_xform_plan_destroy", "fdlp_xform_plan_info", "fdlp_xform_plan_dispatch",
+             "fdlp_xform_compute"]
     src = open(os.path.join(ROOT, "include", "fdlp.h")).read()
     declared = set(re.findall(r"\b(fdlp_[a-z0-9_]+)\s*\(", src))
     for n in names:
         assert n in declared and n in _lib.SIGNATURES and hasattr(_lib.lib, n), n
     assert sorted(n for n in _lib.SIGNATURES if "xform" in n) == sorted(names)
-    assert "#define FDLP_ABI_VERSION 12" in src and _lib.lib.fdlp_abi_version() == 12
+    assert "#define FDLP_ABI_VERSION 13" in src and _lib.lib.fdlp_abi_version() == 13
     # a host-only plan refuses to compute, and null arguments are refused
     import ctypes
     from speech_recognition_tools_amd._lib import FdlpError, FdlpPostBatchC, check

@@ -385,7 +385,7 @@ def test_entry_points_are_declared_and_exported():
     declared = set(re.findall(r"\b(fdlp_[a-z0-9_]+)\s*\(", src))
     for n in names:
         assert n in declared and n in _lib.SIGNATURES and hasattr(_lib.lib, n), n
-    assert "#define FDLP_ABI_VERSION 12" in src and _lib.lib.fdlp_abi_version() == 12 and _lib.ABI_VERSION == 12
+    assert "#define FDLP_ABI_VERSION 13" in src and _lib.lib.fdlp_abi_version() == 13 and _lib.ABI_VERSION == 13
     assert "#define FDLP_VENC_MAX_CONV 8" in src and _lib.FDLP_VENC_MAX_CONV == 8
     # the stage kinds of the public plan did not grow: the internal ones are refused there
     from speech_recognition_tools_amd.rnn import RnnPlan
